@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- statSTR + dumpSTR hot path on synthetic many-sample call sets.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N ...`
   (one rank per GPU).  Rank 0 prints ONE JSON line.
+  A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, the per-kernel
+  averages of the timed steps and their rooflines).  --dump-outputs DIR writes what the last timed step computed
+  (dump_outputs; the inputs depend on --seed / --loci / --samples only, so two builds can be compared array by array).
+  --full adds everything below that is not the headline: the parity check, the box stream probe, the CPU baselines
+  and the extras.
 
 Workload (BASELINE.json metric / configs[3]): statSTR full statistics + dumpSTR
 call- and locus-level filters on a HipSTR-shape call set of 100 000 loci x
@@ -35,11 +40,11 @@ latency-bound rest beside the call-filter kernel on queues 1 and 2 -- dumpSTR's 
 the step on queue 2 (Workload.step / flush).  All work of the K steps ends inside the timed region (flush + trk_sync).
 torch is imported only for N > 1 (rendezvous, barrier, max-over-ranks), never for compute.
 
-Parity inside the bench: after the timed region EVERY locus of the shard is checked against the compiled C
+Parity inside the bench (--full): after the timed region EVERY locus of the shard is checked against the compiled C
 restatement of the reference's algorithm (oracle/fullsize.py: counts, 11 statistics, filter masks, masked
 genotypes, sample_info, locus filter decisions, loc_info) -- `parity_rows_checked` == loci of the shard.
 
-Extras (N = 1 only, each outside the timed region of the headline metric):
+Extras (--full, N = 1 only, each outside the timed region of the headline metric):
   strong_shard    the same step at 100000/N loci for N = 2, 4, 8 on this one GPU through a 1-rank RCCL
                   communicator: what one of N ranks does in the strong-scaled run, with the predicted scaling
                   efficiency (t_100k / N) / t_shard
@@ -83,7 +88,15 @@ def parse():
     ap.add_argument('--no-check', action='store_true')
     ap.add_argument('--no-assoc', action='store_true', help='skip the associaTR scan timing (the "associatr_scan" extra)')
     ap.add_argument('--no-extras', action='store_true', help='skip strong_shard / config1 / config2')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the every-locus parity check, the CPU baselines, the associaTR scan, the '
+                         'box stream probe and the extras (each can be switched off by its --no-... option)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (dump_outputs)')
+    args = ap.parse_args()
+    if not args.full:       # a plain run: set up, warm up, time the steps, (dump), print the line
+        args.no_check = args.no_cpu_baseline = args.no_assoc = args.no_extras = True
+    return args
 
 
 FILTERS_DPQ = None
@@ -1138,6 +1151,61 @@ def end_to_end_extra(eng, seed):
     return out
 
 
+DUMP_TOTAL_BYTES = 60 * 10 ** 6     # all files of one --dump-outputs together (below 64 MB with their headers)
+DUMP_ROWWISE_BYTES = 2 ** 28        # a sampled array above this size is never downloaded whole
+
+
+def dump_outputs(wl, out_dir, seed):
+    """--dump-outputs: what a caller of Workload.step holds after the last timed step, one <name>.npy per array --
+    statSTR's rows (counts, integer and float statistics of GT), dumpSTR's (the same of the masked genotypes GT', the
+    masked genotypes and the filter mask, the per-sample counters, the locus filter decisions, loc_info).  Floats and
+    integers wider than 16 bits as float64 (exact), 16-bit integers as float32.  Every array gets the same share of
+    DUMP_TOTAL_BYTES; one that is larger is cut to a sample of its rows (of its elements when it is a single row), the
+    same sorted draw of a generator seeded by --seed in every run.  Every file holds finite numbers only: a statistic
+    the reference leaves undefined (NaN: heterozygosity, HWE p-value, ... of a locus without calls) is written as 0 and
+    marked in <name>_nonfinite.npy, which every float array has beside it (float32, the array's shape: 0 finite, 1 NaN,
+    2 +inf, 3 -inf).  Returns {name: [shape written, shape of the whole]}."""
+    os.makedirs(out_dir, exist_ok=True)
+    i = wl.last
+    co = wl.call_out
+    arrays = [('stat_allele_count', wl.stats_a[i].allele_count), ('stat_locus_int', wl.stats_a[i].locus_int),
+              ('stat_locus_f64', wl.stats_a[i].locus_f64), ('dump_allele_count', wl.stats_b[i].allele_count),
+              ('dump_locus_int', wl.stats_b[i].locus_int), ('dump_locus_f64', wl.stats_b[i].locus_f64),
+              ('dump_gt_out', co.gt_out), ('dump_filter_mask', co.filter_mask),
+              ('dump_sample_counters', co.sample_counters), ('dump_sample_totaldp', co.sample_totaldp),
+              ('dump_sample_dp_missing', co.sample_dp_missing), ('dump_locus_filter_bits', wl.bits),
+              ('dump_loc_counters', wl.loc_counters)]
+    cap = DUMP_TOTAL_BYTES // len(arrays)
+    rng = np.random.default_rng(seed)
+    written = {}
+    for name, d in arrays:
+        odt = np.float32 if (d.dtype.kind in 'iu' and d.dtype.itemsize <= 2) else np.float64
+        is_float = d.dtype.kind == 'f'
+        osize = np.dtype(odt).itemsize + (4 if is_float else 0)      # (a float array's share pays for its marks too)
+        n_el = int(np.prod(d.shape, dtype=np.int64))
+        if n_el * osize <= cap:
+            a = d.get()
+        else:
+            shape = d.shape
+            while len(shape) > 1 and shape[0] == 1:     # (the statistics carry a leading axis of one sample group)
+                shape = shape[1:]
+            rows = np.sort(rng.choice(shape[0], size=max(1, cap // (n_el // shape[0] * osize)), replace=False))
+            if shape == d.shape and d.nbytes > DUMP_ROWWISE_BYTES:
+                # the two planes are 4 GB each on the device: the drawn rows are fetched one by one
+                a = np.concatenate([d.get_rows(int(r), int(r) + 1) for r in rows])
+            else:
+                a = d.get().reshape(shape)[rows]
+        a = a.astype(odt)
+        if is_float:
+            marks = np.where(np.isnan(a), 1, np.where(np.isposinf(a), 2, np.where(np.isneginf(a), 3, 0))).astype(np.float32)
+            a[marks != 0] = 0.0
+            np.save(os.path.join(out_dir, name + '_nonfinite.npy'), marks)
+        assert a.size * osize <= cap and np.isfinite(a).all()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = [list(a.shape), list(d.shape)]
+    return written
+
+
 def box_stream_probe(eng, wl):
     """The box's own yardstick (it overwrites GT' / mask: call it after everything that reads them): the bare 12 B-in /
     8 B-out stream of the call-filter pass's shape on the same planes (trk_stream_probe), and the clocks the runtime
@@ -1229,6 +1297,10 @@ def main():
     if group is not None:
         elapsed = float(group.allreduce_max_f64(np.array([elapsed]))[0])
         group.barrier()
+
+    dumped = None
+    if args.dump_outputs and rank == 0:     # (N > 1: rank 0's shard)
+        dumped = dump_outputs(wl, args.dump_outputs, args.seed)
 
     check, probe = None, None
     if not args.no_check:
@@ -1337,7 +1409,7 @@ def main():
         a = assoc_extra(wl, args.seed, args.no_check, True, group=group, total_loci=total_loci)
         if rank == 0:
             out.setdefault("extras", {})["associatr_scan"] = a
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         extras = out.setdefault("extras", {})
         if not args.no_assoc:
             extras["associatr_scan"] = assoc_extra(wl, args.seed, args.no_check, args.no_cpu_baseline)
@@ -1362,10 +1434,12 @@ def main():
             extras["config2"] = config2_extra(eng, args.no_check)
             extras["end_to_end"] = end_to_end_extra(eng, args.seed)
     if rank == 0:
-        if probe is None:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if probe is None and args.full:
             probe = box_stream_probe(eng, wl)
         out["roofline"]["box_stream_probe"] = probe
-        if probe.get("achieved"):
+        if probe and probe.get("achieved"):
             out["roofline"]["frac_of_box_stream"] = out["roofline"]["achieved"] / probe["achieved"]
             # flat copies (the driver's parser keeps scalars of this object, not nested ones)
             out["roofline"]["box_stream_ms"] = probe.get("avg_launch_ms")

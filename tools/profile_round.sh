@@ -19,7 +19,7 @@ run3() {   # name, command...: stats pass + two PMC passes of the same command
   ( cd "$repo" && python tools/rocprof_summary.py stats "$(db ${name}_stats)" > "$out/${tag}_${name}_kernel_stats.csv" \
     && python tools/rocprof_summary.py pmc "$(db ${name}_fetch)" "$(db ${name}_write)" > "$out/${tag}_${name}_pmc_fetch_write.csv" )
 }
-run3 bench python "$repo/bench.py" --steps 5 --warmup 2 --no-check --no-cpu-baseline --no-extras
+run3 bench python "$repo/bench.py" --full --steps 5 --warmup 2 --no-check --no-cpu-baseline --no-extras
 run3 configs python "$repo/tools/config_probe.py"
 run3 qc python "$repo/tools/qc_probe.py" --iters 3
 # round 5: the call-filter pass's builds one by one -- the 13 B compact build dumpSTR's command line launches, the HipSTR
