@@ -713,6 +713,76 @@ typedef struct {
 } trk_qc_out;
 int trk_qc_reduce(trk_ctx* ctx, const trk_batch* in, const trk_qc_params* prm, trk_qc_out* out);
 
+/* ---- compareSTR: concordance of two call sets (trtools/compareSTR/compareSTR.py:508-693) ---------------------
+ * A batch of L matched record pairs over S shared samples, both sides in shared-sample column order.  Per side:
+ *   gt          [L, S, P] int16 allele indices, -1 no call, -2 a haplotype the sample lacks (lower ploidy)
+ *   allele_off  [L+1] offsets into the side's per-allele tables
+ *   seq_id / len_id [sumA] uint16 JOINT ids of the pair: two ids (of either side) are equal exactly when
+ *               GetStringGenotypes / GetLengthGenotypes would give equal values (:574-575, :596-597); < 0xfffe
+ *   dlen        [sumA] float64: the allele's length minus len(record1.ref_allele) / len(record1.motif) (:548, :606)
+ *   phased      [L, S] uint8 (the native reader's phase plane) or NULL
+ * dlen_absent [L]: -2 - reflen, what a -2 haplotype adds to the sums (tr_harmonizer.py:1239 leaves -2 in place).
+ * Semantics, per locus l:
+ *   both-called: no -1 haplotype on either side (GetCalledSamples strict, the rule of TRK_LI_N_CALLED; :550-553);
+ *     numcalls == 0: the locus contributes to nothing (:555-556) and its flags are 0.
+ *   TRK_CMP_F_PLOIDY: a both-called sample has different numbers of non -2 entries on the two sides (:568-572).
+ *   phasedness (:578-584), only with both phase planes and ignore_phasing == 0: over the both-called samples
+ *     unphased = !ph1 & !ph2; all unphased -> sorted mode, none -> ordered mode, else TRK_CMP_F_PHASE (compared as
+ *     sorted).  Otherwise every locus is in sorted mode.
+ *   conc_seq / conc_len: the haplotypes' seq_ids / len_ids agree -- as multisets in sorted mode (:588-590, :598-600:
+ *     equality of sorted tuples does not depend on the order that sorts them), position by position in ordered mode.
+ *   TRK_CMP_F_BAD: a both-called sample holds an allele index >= A_l (as TRK_LI_N_BAD).
+ *   moments (:606-607, :633-640): x = sum_h dlen1[a_h], y = sum_h dlen2[b_h]; sums of x, y, x*x, x*y, y*y over the
+ *     both-called samples, float64, separate multiply and add, a fixed order: a rerun gives the same bits.
+ * Per sample over the batch (:561, :594, :604): numcalls, conc_seq, conc_len, ADDED INTO sample_int.
+ * FORMAT stratification (:642-693): n_fields <= TRK_CMP_MAX_FIELDS, each with HOST edges e_0..e_n (ascending), one
+ *   single-column plane per side that stratify_file needs (0: both sides must fall in the same bin, 1 / 2: that side
+ *   alone), at most TRK_CMP_MAX_BINS bins in all.  Bins are [e_i, e_{i+1}), the last closed on both ends.  A value is
+ *   compared the way numpy does: an int32 plane in float64 (the missing sentinel an ordinary very negative number), a
+ *   float32 plane in float32 against the edge rounded to float32; nan fails every comparison.
+ *   slot [L] uint8 or NULL (the locus's period index, < n_slots <= TRK_CMP_MAX_SLOTS; a device array is not checked:
+ *   a value >= n_slots is counted in the LAST slot so that no write leaves the tables -- Engine.compare_calls
+ *   rejects such a host array).
+ *   bin_int int64 [n_slots, NB, 3] (numcalls, conc_seq, conc_len) and bin_f64 float64 [n_slots, NB, 5] are ADDED
+ *   INTO over the batch's loci in a fixed order; NB = 1 + total bins, bin 0 is the unstratified 'ALL' row (:632-640),
+ *   field f's bins follow in field order.  The reference's 'ALL' period is the sum over slots (the caller's).     */
+#define TRK_CMP_MAX_FIELDS 4
+#define TRK_CMP_MAX_BINS 64
+#define TRK_CMP_MAX_SLOTS 32
+enum { TRK_CMP_F_PLOIDY = 1, TRK_CMP_F_PHASE = 2, TRK_CMP_F_BAD = 4 };
+typedef struct {
+    const int16_t* gt;
+    const int32_t* allele_off;
+    const uint16_t* seq_id;
+    const uint16_t* len_id;
+    const double* dlen;
+    const uint8_t* phased;
+} trk_compare_side;
+typedef struct {
+    trk_plane plane[2];      /* TRK_DT_I32 / TRK_DT_F32, ncol 1, [L, S]; data NULL on a side stratify_file leaves out */
+    const double* edges;     /* HOST, n_edges >= 2 values                                                          */
+    int32_t n_edges;
+    int32_t stratify_file;   /* 0, 1 or 2                                                                          */
+} trk_compare_field;
+typedef struct {
+    int32_t n_loci, n_samples, ploidy;
+    int32_t n_pad_samples;   /* the last columns of every row are padding (-1 on both sides); sample_int is
+                                [3, n_samples - n_pad_samples]                                                     */
+    trk_compare_side side[2];
+    const double* dlen_absent;
+    const uint8_t* slot;
+    int32_t n_slots, ignore_phasing, n_fields, reserved;
+    trk_compare_field field[TRK_CMP_MAX_FIELDS];
+} trk_compare_in;
+typedef struct {
+    int32_t* locus_int;      /* [L, 4]: numcalls, sum conc_seq, sum conc_len, TRK_CMP_F_* (written)                */
+    double* locus_f64;       /* [L, 5]: sums of x, y, x*x, x*y, y*y (written)                                      */
+    int64_t* sample_int;     /* [3, S]: numcalls, conc_seq, conc_len (added into)                                  */
+    int64_t* bin_int;        /* [n_slots, NB, 3] (added into)                                                      */
+    double* bin_f64;         /* [n_slots, NB, 5] (added into)                                                      */
+} trk_compare_out;
+int trk_compare(trk_ctx* ctx, const trk_compare_in* in, trk_compare_out* out);
+
 /* Two-sided Student-t tail 2*sf(|t|, df) == scipy.stats.t.sf(|t|, df)*2 (the third-party call
  * behind statsmodels' pvalues); host double, same code as the device finaliser.              */
 double trk_student_t_two_sided(double t, double df);

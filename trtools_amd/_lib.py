@@ -110,6 +110,33 @@ class QcOut(C.Structure):
                 ('sample_qual_n', C.c_void_p), ('locus_qual_sum', C.c_void_p), ('locus_qual_n', C.c_void_p)]
 
 
+# trk_compare (include/trk.h): compareSTR's concordance pass over a batch of matched record pairs
+CMP_MAX_FIELDS, CMP_MAX_BINS, CMP_MAX_SLOTS = 4, 64, 32
+CMP_F_PLOIDY, CMP_F_PHASE, CMP_F_BAD = 1, 2, 4
+CMP_N, CMP_SEQ, CMP_LEN, CMP_FLAGS = range(4)
+
+
+class CompareSide(C.Structure):
+    _fields_ = [('gt', C.c_void_p), ('allele_off', C.c_void_p), ('seq_id', C.c_void_p), ('len_id', C.c_void_p),
+                ('dlen', C.c_void_p), ('phased', C.c_void_p)]
+
+
+class CompareField(C.Structure):
+    _fields_ = [('plane', Plane * 2), ('edges', C.c_void_p), ('n_edges', C.c_int32), ('stratify_file', C.c_int32)]
+
+
+class CompareIn(C.Structure):
+    _fields_ = [('n_loci', C.c_int32), ('n_samples', C.c_int32), ('ploidy', C.c_int32), ('n_pad_samples', C.c_int32),
+                ('side', CompareSide * 2), ('dlen_absent', C.c_void_p), ('slot', C.c_void_p),
+                ('n_slots', C.c_int32), ('ignore_phasing', C.c_int32), ('n_fields', C.c_int32), ('reserved', C.c_int32),
+                ('field', CompareField * CMP_MAX_FIELDS)]
+
+
+class CompareOut(C.Structure):
+    _fields_ = [('locus_int', C.c_void_p), ('locus_f64', C.c_void_p), ('sample_int', C.c_void_p),
+                ('bin_int', C.c_void_p), ('bin_f64', C.c_void_p)]
+
+
 class AssocOut(C.Structure):
     _fields_ = [('locus_int', C.c_void_p), ('locus_f64', C.c_void_p), ('allele_count', C.c_void_p)]
 
@@ -193,7 +220,7 @@ EXPORTS = [
     'trk_locus_stats', 'trk_locus_finalize', 'trk_call_filters', 'trk_locus_filters',
     'trk_comm_unique_id', 'trk_comm_init', 'trk_allreduce_sum_i64', 'trk_allgather',
     'trk_binomtest_two_sided', 'trk_binom_pmf', 'trk_binomtest_batch', 'trk_synth_fill', 'trk_synth_fill_gangstr', 'trk_test_set_option', 'trk_test_get_option',
-    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
+    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
     'trk_host_alloc', 'trk_host_free', 'trk_memcpy_h2d_async', 'trk_memcpy_d2h_async', 'trk_queue_sync', 'trk_thread_queue', 'trk_exchange', 'trk_event_record', 'trk_event_wait',
 ]
 
@@ -205,7 +232,7 @@ class TrkError(RuntimeError):
 
 
 # the sources libtrk.so is built from, in the order csrc/Makefile hashes them
-_SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_binom.h', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
+_SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_binom.h', 'csrc/trk_compare.hip', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
             'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
 
 
@@ -357,6 +384,7 @@ def load():
     lib.trk_stream_wait.argtypes = [vp, C.c_int, C.c_int]
     lib.trk_dosages.argtypes = [vp, P(Batch), vp, C.c_int, vp, vp, C.c_int, vp, vp]
     lib.trk_qc_reduce.argtypes = [vp, P(Batch), P(QcParams), P(QcOut)]
+    lib.trk_compare.argtypes = [vp, P(CompareIn), P(CompareOut)]
     lib.trk_parse_samples.argtypes = [vp, P(ParseIn), P(ParseOut)]
     lib.trk_inflate_blocks.argtypes = [vp, P(InflateIn), P(InflateOut)]
     lib.trk_inflate_hook.argtypes = [vp, P(vp), P(vp), P(vp)]

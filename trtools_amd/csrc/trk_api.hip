@@ -921,6 +921,50 @@ int trk_qc_reduce(trk_ctx* ctx, const trk_batch* in, const trk_qc_params* prm, t
     return TRK_OK;
 }
 
+int trk_compare(trk_ctx* ctx, const trk_compare_in* in, trk_compare_out* out) {
+    if (!ctx) return TRK_ERR_ARG;
+    if (!in || !out) return fail(ctx, TRK_ERR_ARG, "compare: arguments are NULL");
+    if (in->n_loci < 0 || in->n_samples < 0 || in->ploidy < 1 || in->ploidy > TRK_MAX_PLOIDY)
+        return fail(ctx, TRK_ERR_ARG, "compare: loci %d, samples %d, ploidy %d", in->n_loci, in->n_samples, in->ploidy);
+    if (in->n_pad_samples < 0 || (in->n_pad_samples > 0 && in->n_pad_samples >= in->n_samples))
+        return fail(ctx, TRK_ERR_ARG, "compare: n_pad_samples %d outside [0, n_samples)", in->n_pad_samples);
+    if (in->n_slots < 1 || in->n_slots > TRK_CMP_MAX_SLOTS)
+        return fail(ctx, TRK_ERR_ARG, "compare: n_slots %d outside [1,%d]", in->n_slots, TRK_CMP_MAX_SLOTS);
+    if (in->n_fields < 0 || in->n_fields > TRK_CMP_MAX_FIELDS)
+        return fail(ctx, TRK_ERR_ARG, "compare: n_fields %d outside [0,%d]", in->n_fields, TRK_CMP_MAX_FIELDS);
+    if (in->n_loci == 0 || in->n_samples == 0) return TRK_OK;
+    int n_bins = 0;
+    for (int f = 0; f < in->n_fields; ++f) {
+        const trk_compare_field& fl = in->field[f];
+        if (!fl.edges || fl.n_edges < 2) return fail(ctx, TRK_ERR_ARG, "compare: field %d needs at least two edges", f);
+        if (fl.stratify_file < 0 || fl.stratify_file > 2)
+            return fail(ctx, TRK_ERR_ARG, "compare: stratify_file %d of field %d", fl.stratify_file, f);
+        int dt = -1;
+        for (int k = 0; k < 2; ++k) {
+            if (fl.stratify_file == 2 - k) continue;   // the side the rule does not read
+            const trk_plane& p = fl.plane[k];
+            if (!p.data || p.ncol != 1 || (p.dtype != TRK_DT_I32 && p.dtype != TRK_DT_F32) || (dt >= 0 && dt != p.dtype))
+                return fail(ctx, TRK_ERR_ARG, "compare: field %d wants single-column int32 / float32 planes of one type", f);
+            dt = p.dtype;
+        }
+        n_bins += fl.n_edges - 1;
+    }
+    if (n_bins > TRK_CMP_MAX_BINS) return fail(ctx, TRK_ERR_ARG, "compare: %d bins, at most %d", n_bins, TRK_CMP_MAX_BINS);
+    for (int k = 0; k < 2; ++k) {
+        const trk_compare_side& s = in->side[k];
+        if (!s.gt || !s.allele_off || !s.seq_id || !s.len_id || !s.dlen)
+            return fail(ctx, TRK_ERR_ARG, "compare: genotypes / joint allele tables of side %d are NULL", k + 1);
+    }
+    if (!in->dlen_absent) return fail(ctx, TRK_ERR_ARG, "compare: dlen_absent is NULL");
+    if (!out->locus_int || !out->locus_f64 || !out->sample_int || !out->bin_int || !out->bin_f64)
+        return fail(ctx, TRK_ERR_ARG, "compare: outputs are NULL");
+    (void)hipSetDevice(ctx->device);
+    void* ws = workspace_for_queue(ctx, trk::compare_workspace_bytes(*in, ctx->n_cu));
+    if (!ws) return fail(ctx, TRK_ERR_HIP, "compare: workspace allocation failed");
+    HIPCHK(ctx, trk::launch_compare(*in, *out, ws, ctx->n_cu, ctx->s()));
+    return TRK_OK;
+}
+
 int trk_parse_samples(trk_ctx* ctx, const trk_parse_in* in, trk_parse_out* out) {
     if (!ctx) return TRK_ERR_ARG;
     if (!in || !out) return fail(ctx, TRK_ERR_ARG, "parse_samples: arguments are NULL");

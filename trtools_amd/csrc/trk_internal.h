@@ -105,6 +105,10 @@ hipError_t launch_stream_probe(const void* const* in, int n_in, void* const* out
 size_t qc_workspace_bytes(const trk_batch& b, const float* quality, int n_cu);
 hipError_t launch_qc_reduce(const trk_batch& b, const trk_qc_params& prm, const trk_qc_out& out, void* workspace,
                             int n_cu, hipStream_t stream);
+// compareSTR's concordance pass (trk_compare.hip)
+size_t compare_workspace_bytes(const trk_compare_in& in, int n_cu);
+hipError_t launch_compare(const trk_compare_in& in, const trk_compare_out& out, void* workspace, int n_cu,
+                          hipStream_t stream);
 
 hipError_t launch_parse_samples(const trk_parse_in& in, const trk_parse_out& out, hipStream_t stream);
 hipError_t launch_format_samples(const trk_format_in& in, const trk_format_out& out, int pass, hipStream_t stream);

@@ -1024,6 +1024,98 @@ class Engine:
         self._chk(self.lib.trk_qc_reduce(self.ctx, C.byref(batch.struct), C.byref(prm), C.byref(out)))
         return res
 
+    def compare_accumulators(self, n_samples, n_slots=1, n_bins=0):
+        """Zeroed accumulators of ``compare_calls`` for one run: sample_int int64 [3, S], bin_int int64
+        [n_slots, 1 + n_bins, 3], bin_f64 float64 [n_slots, 1 + n_bins, 5]."""
+        return dict(sample_int=self.zeros((3, n_samples), np.int64),
+                    bin_int=self.zeros((n_slots, 1 + n_bins, 3), np.int64),
+                    bin_f64=self.zeros((n_slots, 1 + n_bins, 5), np.float64))
+
+    def compare_calls(self, sides, dlen_absent, acc=None, slot=None, n_slots=1, fields=(), ignore_phasing=False,
+                      pad=True):
+        """trk_compare (compareSTR's concordance pass, include/trk.h) over a batch of matched record pairs.
+        ``sides``: two dicts with 'gt' int16 [L, S, P] (-1 no call, -2 absent haplotype), 'allele_off' int32 [L+1],
+        the JOINT tables 'seq_id' / 'len_id' uint16 [sumA] and 'dlen' float64 [sumA], and optionally 'phased' uint8
+        [L, S]; every entry a host array or a DeviceArray.  ``fields``: dicts with 'planes' (a pair of int32 /
+        float32 [L, S] arrays, None on a side ``stratify_file`` leaves out), 'edges' and 'stratify_file'.  ``acc``:
+        the accumulators to add into (``compare_accumulators``; made when None).  Host diploid genotypes and planes of
+        rows that are no multiple of four samples are padded with no-calls on both sides (``pad``), as compute.py pads
+        a batch; device arrays are taken as they are.  Returns a dict of device arrays: locus_int int32 [L, 4],
+        locus_f64 float64 [L, 5] of this batch and the accumulators."""
+        g0 = sides[0]['gt']
+        nl, ns, pl = (int(x) for x in g0.shape)
+        host = not any(isinstance(sd['gt'], DeviceArray) for sd in sides)
+        n_pad = (-ns) % 4 if (pad and host and pl == 2 and ns > 0) else 0
+        keep = []
+
+        def dev(x, dt, fill=None):
+            if isinstance(x, DeviceArray):
+                return x
+            x = np.ascontiguousarray(x, dtype=dt)
+            if fill is not None and n_pad:
+                shape = list(x.shape)
+                shape[1] = n_pad
+                x = np.concatenate([x, np.full(shape, fill, dtype=dt)], axis=1)
+            d = self.upload(x, dt)
+            keep.append(d)
+            return d
+        edges_keep = []
+        cin = L.CompareIn()
+        cin.n_loci, cin.n_samples, cin.ploidy, cin.n_pad_samples = nl, ns + n_pad, pl, n_pad
+        for k, sd in enumerate(sides):
+            for name in ('seq_id', 'len_id'):
+                if not isinstance(sd[name], DeviceArray) and np.size(sd[name]) and int(np.max(sd[name])) >= 0xfffe:
+                    raise ValueError("joint allele ids must be below 0xfffe")
+            s = cin.side[k]
+            s.gt = dev(sd['gt'], np.int16, -1).ptr
+            s.allele_off = dev(sd['allele_off'], np.int32).ptr
+            s.seq_id = dev(sd['seq_id'], np.uint16).ptr
+            s.len_id = dev(sd['len_id'], np.uint16).ptr
+            s.dlen = dev(sd['dlen'], np.float64).ptr
+            ph = sd.get('phased')
+            s.phased = dev(ph, np.uint8, 0).ptr if ph is not None else None
+        cin.dlen_absent = dev(dlen_absent, np.float64).ptr
+        if slot is not None and not isinstance(slot, DeviceArray) and np.size(slot) \
+                and not 0 <= int(np.min(slot)) <= int(np.max(slot)) < int(n_slots):
+            raise ValueError("slot values must lie in [0, n_slots)")
+        cin.slot = dev(slot, np.uint8).ptr if slot is not None else None
+        cin.n_slots, cin.ignore_phasing, cin.n_fields = int(n_slots), 1 if ignore_phasing else 0, len(fields)
+        if len(fields) > L.CMP_MAX_FIELDS:
+            raise ValueError("at most %d stratify fields" % L.CMP_MAX_FIELDS)
+        n_bins = 0
+        for f, fd in enumerate(fields):
+            e = np.ascontiguousarray(fd['edges'], dtype=np.float64)
+            edges_keep.append(e)
+            n_bins += e.size - 1
+            cf = cin.field[f]
+            cf.edges, cf.n_edges, cf.stratify_file = e.ctypes.data, e.size, int(fd['stratify_file'])
+            for k in range(2):
+                p = fd['planes'][k]
+                if p is None or cf.stratify_file == 2 - k:
+                    continue
+                flt = np.dtype(p.dtype).kind == 'f'
+                d = dev(p, np.float32 if flt else np.int32, np.float32('nan') if flt else -2 ** 31)
+                cf.plane[k] = L.Plane(d.ptr, L.DT_F32 if flt else L.DT_I32, 1)
+        if n_bins > L.CMP_MAX_BINS:
+            raise ValueError("at most %d stratification bins in all" % L.CMP_MAX_BINS)
+        if acc is None:
+            acc = self.compare_accumulators(ns, n_slots, n_bins)
+        if acc['sample_int'].shape != (3, ns) or acc['bin_int'].shape != (int(n_slots), 1 + n_bins, 3) \
+                or acc['bin_f64'].shape != (int(n_slots), 1 + n_bins, 5):
+            raise ValueError("accumulators do not fit this batch (compare_accumulators)")
+        res = dict(acc)
+        res['locus_int'] = self.zeros((nl, 4), np.int32)
+        res['locus_f64'] = self.zeros((nl, 5), np.float64)
+        out = L.CompareOut(res['locus_int'].ptr, res['locus_f64'].ptr, acc['sample_int'].ptr, acc['bin_int'].ptr,
+                           acc['bin_f64'].ptr)
+        self._chk(self.lib.trk_compare(self.ctx, C.byref(cin), C.byref(out)))
+        if keep:
+            self.sync()                       # (the uploads go back to the pool: the kernels must be done with them)
+            with self.idle_frees():
+                for d in keep:
+                    d.free()
+        return res
+
     def student_t_two_sided(self, t, df):
         return float(self.lib.trk_student_t_two_sided(float(t), float(df)))
 
