@@ -783,6 +783,49 @@ typedef struct {
 } trk_compare_out;
 int trk_compare(trk_ctx* ctx, const trk_compare_in* in, trk_compare_out* out);
 
+/* ---- prancSTR: the mosaic allele fit of every call (trtools/prancSTR/prancSTR.py:56-117, :357-385, :549-562) -----
+ * Per locus: stutter [L, 3] float64 (u, d, rho), the reference's defaults and zero-replacements (:499-518) already
+ *   applied; P[delta], delta = -100 .. 100, is StutterProb (:26-54): 1 - u - d at 0, u rho (1 - rho)^(delta - 1) above,
+ *   d rho (1 - rho)^(-delta - 1) below, the powers by repeated multiplication.  Deltas are confined to +-100.
+ * Per call c = l * S + s: ab[c] = (A, B) in repeat units, TRK_MOSAIC_NOCALL_AB in either: no call; the distinct read
+ *   values read_val[read_off[c] .. read_off[c+1]) STRICTLY ASCENDING (|r| <= TRK_MOSAIC_MAX_ABS) with their counts
+ *   read_cnt (> 0).  n_reads is the length of read_val / read_cnt: offsets outside it are not followed.
+ * status[c], the low four bits (:549-562, "A not in reads or (B not in reads and not output_all)" as Python reads it):
+ *   TRK_MOSAIC_FIT          fitted
+ *   TRK_MOSAIC_NOCALL       no call, or no reads
+ *   TRK_MOSAIC_UNSUPPORTED  A is not among the reads, or B is not and TRK_MOSAIC_OUTPUT_ALL is not set
+ *   TRK_MOSAIC_SINGLE       a single distinct read value, without TRK_MOSAIC_OUTPUT_ALL
+ *   TRK_MOSAIC_BAD          offsets outside [0, n_reads], values not strictly ascending or out of range, a count <= 0,
+ *                           or more than TRK_MOSAIC_MAX_SPAN candidates (max r - min r + 7)
+ *   TRK_MOSAIC_FIT_ALL (MaximizeMosaicLikelihoodBoth called on its own, which looks at no evidence): every call with a
+ *   genotype and valid reads is fitted.
+ *   A call that is not fitted has c = support = 0 and nan in the float outputs.
+ * The fit: LL_k(C, f) = sum_j n_j log(L_kj), LL = max(LL_1, LL_2) (LL_1 unless LL_2 is larger),
+ *     L_1j = P[r_j-A]/2 + (1/2 - f) P[r_j-B] + f P[r_j-C],   L_2j = (1/2 - f) P[r_j-A] + P[r_j-B]/2 + f P[r_j-C],
+ *   every L_kj = 1e-199 when C is A or B.
+ *   C step at fixed f: the first candidate of min r - 3 .. max r + 3 with the strictly largest LL (:140-155).
+ *   f step at fixed C: the EXACT maximiser of LL(C, .) on [0, 0.5], not SLSQP's stopping point: LL_k is concave, so f_k*
+ *     is 0 if LL_k'(0) <= 0, 0.5 if LL_k'(0.5) >= 0, else the root of LL_k'; the f_k* of the larger LL_k(f_k*), branch 1
+ *     on a tie.
+ *   Alternation (:89-117): f = 0.01, a C step and an f step, then pairs of them until |f - f_prev| < 0.01 and
+ *     (f < 1e-6 or C == C_prev); after 101 pairs in all TRK_MOSAIC_NONCONV is set.  f == 0.0: no C (TRK_MOSAIC_NO_C,
+ *     c = 0).
+ *   Test (:357-385): ll_fit = LL(C, f), ll_null = LL(C, 0), t = -2 (ll_null - ll_fit),
+ *     pval = 0.5 [t <= 0] + 0.5 chi2.sf(t, 2) = 0.5 [t <= 0] + 0.5 exp(-max(t, 0) / 2).  Without C: ll_fit = ll_null
+ *     (the likelihood of the genotype alone), pval = 1.
+ *   support: the count of the read value equal to C, 0 without C.
+ * Outputs are dense [L, S].  float64 throughout, separate multiply and add; no atomics: a rerun gives the same bits. */
+#define TRK_MOSAIC_NOCALL_AB INT32_MIN
+#define TRK_MOSAIC_MAX_SPAN 4096
+#define TRK_MOSAIC_MAX_ABS (1 << 30)
+enum { TRK_MOSAIC_OUTPUT_ALL = 1, TRK_MOSAIC_FIT_ALL = 2 };
+enum { TRK_MOSAIC_FIT = 0, TRK_MOSAIC_NOCALL = 1, TRK_MOSAIC_UNSUPPORTED = 2, TRK_MOSAIC_SINGLE = 3, TRK_MOSAIC_BAD = 4,
+       TRK_MOSAIC_NO_C = 0x10, TRK_MOSAIC_NONCONV = 0x20 };
+int trk_mosaic_fit(trk_ctx* ctx, int32_t n_loci, int32_t n_samples, const int32_t* ab, const int32_t* read_off,
+                   const int32_t* read_val, const int32_t* read_cnt, int64_t n_reads, const double* stutter,
+                   int32_t flags, int32_t* c, double* f, double* pval, double* ll_fit, double* ll_null,
+                   int32_t* support, uint8_t* status);
+
 /* Two-sided Student-t tail 2*sf(|t|, df) == scipy.stats.t.sf(|t|, df)*2 (the third-party call
  * behind statsmodels' pvalues); host double, same code as the device finaliser.              */
 double trk_student_t_two_sided(double t, double df);

@@ -110,6 +110,11 @@ class QcOut(C.Structure):
                 ('sample_qual_n', C.c_void_p), ('locus_qual_sum', C.c_void_p), ('locus_qual_n', C.c_void_p)]
 
 
+# trk_mosaic_fit (include/trk.h): prancSTR's per-call model
+MOSAIC_NOCALL_AB, MOSAIC_MAX_SPAN, MOSAIC_MAX_ABS, MOSAIC_OUTPUT_ALL, MOSAIC_FIT_ALL = -2 ** 31, 4096, 1 << 30, 1, 2
+MOSAIC_FIT, MOSAIC_NOCALL, MOSAIC_UNSUPPORTED, MOSAIC_SINGLE, MOSAIC_BAD = range(5)
+MOSAIC_NO_C, MOSAIC_NONCONV = 0x10, 0x20
+
 # trk_compare (include/trk.h): compareSTR's concordance pass over a batch of matched record pairs
 CMP_MAX_FIELDS, CMP_MAX_BINS, CMP_MAX_SLOTS = 4, 64, 32
 CMP_F_PLOIDY, CMP_F_PHASE, CMP_F_BAD = 1, 2, 4
@@ -220,7 +225,7 @@ EXPORTS = [
     'trk_locus_stats', 'trk_locus_finalize', 'trk_call_filters', 'trk_locus_filters',
     'trk_comm_unique_id', 'trk_comm_init', 'trk_allreduce_sum_i64', 'trk_allgather',
     'trk_binomtest_two_sided', 'trk_binom_pmf', 'trk_binomtest_batch', 'trk_synth_fill', 'trk_synth_fill_gangstr', 'trk_test_set_option', 'trk_test_get_option',
-    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
+    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_mosaic_fit', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
     'trk_host_alloc', 'trk_host_free', 'trk_memcpy_h2d_async', 'trk_memcpy_d2h_async', 'trk_queue_sync', 'trk_thread_queue', 'trk_exchange', 'trk_event_record', 'trk_event_wait',
 ]
 
@@ -233,7 +238,7 @@ class TrkError(RuntimeError):
 
 # the sources libtrk.so is built from, in the order csrc/Makefile hashes them
 _SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_binom.h', 'csrc/trk_compare.hip', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
-            'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
+            'csrc/trk_mosaic.hip', 'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
 
 
 def source_digest():
@@ -385,6 +390,7 @@ def load():
     lib.trk_dosages.argtypes = [vp, P(Batch), vp, C.c_int, vp, vp, C.c_int, vp, vp]
     lib.trk_qc_reduce.argtypes = [vp, P(Batch), P(QcParams), P(QcOut)]
     lib.trk_compare.argtypes = [vp, P(CompareIn), P(CompareOut)]
+    lib.trk_mosaic_fit.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int32] + [vp] * 7
     lib.trk_parse_samples.argtypes = [vp, P(ParseIn), P(ParseOut)]
     lib.trk_inflate_blocks.argtypes = [vp, P(InflateIn), P(InflateOut)]
     lib.trk_inflate_hook.argtypes = [vp, P(vp), P(vp), P(vp)]

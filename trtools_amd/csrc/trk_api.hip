@@ -965,6 +965,28 @@ int trk_compare(trk_ctx* ctx, const trk_compare_in* in, trk_compare_out* out) {
     return TRK_OK;
 }
 
+int trk_mosaic_fit(trk_ctx* ctx, int32_t n_loci, int32_t n_samples, const int32_t* ab, const int32_t* read_off,
+                   const int32_t* read_val, const int32_t* read_cnt, int64_t n_reads, const double* stutter,
+                   int32_t flags, int32_t* c, double* f, double* pval, double* ll_fit, double* ll_null,
+                   int32_t* support, uint8_t* status) {
+    if (!ctx) return TRK_ERR_ARG;
+    if (n_loci < 0 || n_samples < 0 || n_reads < 0 || n_reads > INT32_MAX || (int64_t)n_loci * n_samples >= INT32_MAX)
+        return fail(ctx, TRK_ERR_ARG, "mosaic fit: loci %d, samples %d, reads %lld (calls and reads are indexed in int32)",
+                    n_loci, n_samples, (long long)n_reads);
+    if (n_loci == 0 || n_samples == 0) return TRK_OK;
+    if (!ab || !read_off || !stutter || (n_reads > 0 && (!read_val || !read_cnt)))
+        return fail(ctx, TRK_ERR_ARG, "mosaic fit: inputs are NULL");
+    if (!c || !f || !pval || !ll_fit || !ll_null || !support || !status)
+        return fail(ctx, TRK_ERR_ARG, "mosaic fit: outputs are NULL");
+    const trk::trk_mosaic_in in = {n_loci, n_samples, ab, read_off, read_val, read_cnt, n_reads, stutter, flags};
+    const trk::trk_mosaic_out out = {c, f, pval, ll_fit, ll_null, support, status};
+    (void)hipSetDevice(ctx->device);
+    void* ws = workspace_for_queue(ctx, trk::mosaic_workspace_bytes((int64_t)n_loci * n_samples));
+    if (!ws) return fail(ctx, TRK_ERR_HIP, "mosaic fit: workspace allocation failed");
+    HIPCHK(ctx, trk::launch_mosaic_fit(in, out, ws, ctx->n_cu, ctx->s()));
+    return TRK_OK;
+}
+
 int trk_parse_samples(trk_ctx* ctx, const trk_parse_in* in, trk_parse_out* out) {
     if (!ctx) return TRK_ERR_ARG;
     if (!in || !out) return fail(ctx, TRK_ERR_ARG, "parse_samples: arguments are NULL");

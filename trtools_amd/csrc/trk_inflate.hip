@@ -786,4 +786,9 @@ hipError_t launch_line_index(const uint8_t* text, int64_t n, int tabs_in, const 
                        ws.packed, ws.packed_cap, ws.nl_cap);
     return hipGetLastError();
 }
+// k_scan_u32 for the other translation units (the mosaic pass's compaction)
+hipError_t launch_scan_u32(uint32_t* counts, int n, uint32_t* total, hipStream_t stream) {
+    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, stream, counts, n, total);
+    return hipGetLastError();
+}
 }  // namespace trk

@@ -109,6 +109,31 @@ hipError_t launch_qc_reduce(const trk_batch& b, const trk_qc_params& prm, const 
 size_t compare_workspace_bytes(const trk_compare_in& in, int n_cu);
 hipError_t launch_compare(const trk_compare_in& in, const trk_compare_out& out, void* workspace, int n_cu,
                           hipStream_t stream);
+// prancSTR's mosaic fit (trk_mosaic.hip); trk_mosaic_fit's arguments, gathered
+struct trk_mosaic_in {
+    int n_loci, n_samples;
+    const int32_t* ab;
+    const int32_t* read_off;
+    const int32_t* read_val;
+    const int32_t* read_cnt;
+    int64_t n_reads;
+    const double* stutter;
+    int flags;
+};
+struct trk_mosaic_out {
+    int32_t* c;
+    double* f;
+    double* pval;
+    double* ll_fit;
+    double* ll_null;
+    int32_t* support;
+    uint8_t* status;
+};
+size_t mosaic_workspace_bytes(int64_t n_calls);
+hipError_t launch_mosaic_fit(const trk_mosaic_in& in, const trk_mosaic_out& out, void* workspace, int n_cu,
+                             hipStream_t stream);
+// exclusive scan of counts[0 .. n) in place by one workgroup, the sum to *total (trk_inflate.hip)
+hipError_t launch_scan_u32(uint32_t* counts, int n, uint32_t* total, hipStream_t stream);
 
 hipError_t launch_parse_samples(const trk_parse_in& in, const trk_parse_out& out, hipStream_t stream);
 hipError_t launch_format_samples(const trk_format_in& in, const trk_format_out& out, int pass, hipStream_t stream);

@@ -1116,6 +1116,43 @@ class Engine:
                     d.free()
         return res
 
+    def mosaic_fit(self, ab, read_off, read_val, read_cnt, stutter, output_all=False, fit_all=False):
+        """trk_mosaic_fit (prancSTR's per-call model, include/trk.h) over the dense [L, S] calls.  ``ab`` int32
+        [L, S, 2] in repeat units (``_lib.MOSAIC_NOCALL_AB``: no call), the reads as CSR arrays -- ``read_off`` int32
+        [L*S + 1], ``read_val`` strictly ascending per call, ``read_cnt`` -- and ``stutter`` float64 [L, 3] (u, d,
+        rho); every entry a host array or a DeviceArray.  ``fit_all``: fit every call with a genotype and reads,
+        whatever the evidence (a call of MaximizeMosaicLikelihoodBoth on its own).  Returns a dict of device arrays,
+        each [L, S]: C, support (int32), f, pval, ll_fit, ll_null (float64) and status (uint8: ``_lib.MOSAIC_*``).
+        f is the exact maximiser of the likelihood on [0, 0.5], not SLSQP's stopping point."""
+        nl, ns = int(ab.shape[0]), int(ab.shape[1])
+        keep = []
+
+        def dev(x, dt):
+            if isinstance(x, DeviceArray):
+                return x
+            d = self.upload(np.ascontiguousarray(x, dtype=dt), dt)
+            keep.append(d)
+            return d
+        n_reads = int(np.prod(read_val.shape))
+        if int(np.prod(read_off.shape)) != nl * ns + 1 or int(np.prod(read_cnt.shape)) != n_reads \
+                or tuple(ab.shape) != (nl, ns, 2) or tuple(stutter.shape) != (nl, 3):
+            raise ValueError("mosaic_fit: ab [L, S, 2], read_off [L*S + 1], read_val / read_cnt of one length, stutter [L, 3]")
+        args = [dev(ab, np.int32), dev(read_off, np.int32), dev(read_val, np.int32), dev(read_cnt, np.int32),
+                dev(stutter, np.float64)]
+        res = {k: self.empty((nl, ns), dt) for k, dt in (('C', np.int32), ('f', np.float64), ('pval', np.float64),
+                                                         ('ll_fit', np.float64), ('ll_null', np.float64),
+                                                         ('support', np.int32), ('status', np.uint8))}
+        self._chk(self.lib.trk_mosaic_fit(self.ctx, nl, ns, args[0].ptr, args[1].ptr, args[2].ptr if n_reads else None,
+                                          args[3].ptr if n_reads else None, n_reads, args[4].ptr,
+                                          (L.MOSAIC_OUTPUT_ALL if output_all else 0) | (L.MOSAIC_FIT_ALL if fit_all else 0),
+                                          *[res[k].ptr for k in ('C', 'f', 'pval', 'll_fit', 'll_null', 'support', 'status')]))
+        if keep:
+            self.sync()                       # (the uploads go back to the pool: the kernels must be done with them)
+            with self.idle_frees():
+                for d in keep:
+                    d.free()
+        return res
+
     def student_t_two_sided(self, t, df):
         return float(self.lib.trk_student_t_two_sided(float(t), float(df)))
 
