@@ -826,6 +826,49 @@ int trk_mosaic_fit(trk_ctx* ctx, int32_t n_loci, int32_t n_samples, const int32_
                    int32_t flags, int32_t* c, double* f, double* pval, double* ll_fit, double* ll_null,
                    int32_t* support, uint8_t* status);
 
+/* ---- prancSTR: the read vectors of a batch of records parsed on the device (trtools/prancSTR/prancSTR.py:220-247) ----
+ * What trk_mosaic_fit reads -- ab, read_off, read_val, read_cnt -- made in HBM from the batch's TEXT (text / smp_off /
+ * line_end as for trk_parse_samples) instead of per call in Python.  read_idx[l]: index of the read field (MALLREADS)
+ * among record l's FORMAT keys, -1: the record lacks it (no reads, flag 0); period[l] >= 1.
+ * A call's field is split on ';' and read up to, not including, the first piece without a '|' ('.', an empty field, an
+ * empty tail end it quietly; so does a token with fewer subfields than read_idx).  An entry is -?d{1,9} '|' d{1,9};
+ * value = bp // period (floor); equal values are merged and their counts summed; a count of 0 contributes nothing.
+ * A second '|' in an entry, any other character in one, ten or more digits, a merged count above INT32_MAX, more than
+ * TRK_READS_MAX_ENTRIES entries or a field of more than TRK_READS_MAX_FIELD bytes set TRK_PARSE_HOST on the RECORD, a
+ * wrong number of sample columns TRK_PARSE_COLUMNS: every call of a flagged record has no reads and no genotype here
+ * and the caller parses that record on the host.  A sample token may be of any length.
+ * Optional, all three or none: gt [L, S, 2] as trk_parse_samples leaves it, allele_off [L + 1] and allele_bp [sumA] (an
+ * allele's length in bp minus the reference allele's): ab = floor(allele_bp[gt_h] / period) per haplotype, both
+ * TRK_MOSAIC_NOCALL_AB when either index is negative or not below the record's number of alleles.
+ * The output is ragged: pass 1 writes flags and the complete read_off (read_off[L*S] is the number of entries; more than
+ * INT32_MAX of them: TRK_ERR_DATA), the caller allocates read_val / read_cnt of that length, pass 2 fills them (strictly
+ * ascending values per call, counts > 0) and ab.  `workspace`: TRK_READS_WS_BYTES device bytes, 8-byte aligned, the
+ * caller's, untouched between the passes.  No atomics: a rerun gives the same bytes. */
+#define TRK_READS_MAX_ENTRIES 64
+#define TRK_READS_MAX_FIELD 512
+#define TRK_READS_WS_BYTES(L, S) ((size_t)16 * (size_t)(L) * (size_t)(S) + (size_t)16 * (size_t)(L) + 16)
+typedef struct {
+    const uint8_t* text;       /* device, 16-byte aligned; readable up to the 16-byte chunk that holds the last line_end */
+    int64_t n_bytes;
+    int32_t n_records, n_samples;
+    const int64_t* smp_off;    /* device [n_records] (any alignment of the offsets)                                      */
+    const int64_t* line_end;   /* device [n_records]                                                                     */
+    const int8_t* read_idx;    /* device [n_records]                                                                     */
+    const int32_t* period;     /* device [n_records]                                                                     */
+    const int16_t* gt;         /* optional device [n_records, n_samples, 2]                                              */
+    const int32_t* allele_off; /* optional device [n_records + 1]                                                        */
+    const int32_t* allele_bp;  /* optional device [allele_off[n_records]]                                                */
+} trk_reads_in;
+typedef struct {
+    int32_t* read_off;         /* device [n_records * n_samples + 1] (pass 1 writes, pass 2 reads)                       */
+    uint8_t* flags;            /* device [n_records]: 0 or TRK_PARSE_* bits (pass 1 writes, pass 2 reads)                */
+    void* workspace;           /* device, TRK_READS_WS_BYTES(n_records, n_samples)                                       */
+    int32_t* read_val;         /* device [read_off[n_records * n_samples]] (pass 2)                                      */
+    int32_t* read_cnt;         /* device, the same length (pass 2)                                                       */
+    int32_t* ab;               /* device [n_records, n_samples, 2] (pass 2, with gt)                                     */
+} trk_reads_out;
+int trk_parse_reads(trk_ctx* ctx, const trk_reads_in* in, const trk_reads_out* out, int pass);
+
 /* Two-sided Student-t tail 2*sf(|t|, df) == scipy.stats.t.sf(|t|, df)*2 (the third-party call
  * behind statsmodels' pvalues); host double, same code as the device finaliser.              */
 double trk_student_t_two_sided(double t, double df);

@@ -3,7 +3,7 @@ export TRK_LAB=1   # tools are lab runs: lab knobs are honoured (trtools_amd/_kn
 # Kernels of libtrk.so that use scratch memory, per translation unit, from the compiler's own resource remarks
 # (`-Rpass-analysis=kernel-resource-usage`): name, VGPRs, scratch bytes per lane.  Run from anywhere; no GPU needed.
 cd "$(dirname "$0")/../trtools_amd/csrc" || exit 1
-for f in trk_kernels trk_hwe trk_assoc trk_qc trk_compare trk_mosaic trk_parse trk_api; do
+for f in trk_kernels trk_hwe trk_assoc trk_qc trk_compare trk_mosaic trk_parse trk_reads trk_api; do
     [ -f $f.hip ] || continue
     extra=""; [ $f = trk_hwe ] && extra="-mllvm -disable-machine-licm"
     [ $f = trk_compare ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"

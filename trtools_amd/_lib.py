@@ -171,6 +171,25 @@ class ParseIn(C.Structure):
                 ('gt_idx', C.c_void_p), ('plane_idx', C.c_void_p * PARSE_MAX_PLANES), ('plane_kind', C.c_int32 * PARSE_MAX_PLANES)]
 
 
+# trk_parse_reads (include/trk.h): prancSTR's read vectors parsed on the device
+READS_MAX_ENTRIES, READS_MAX_FIELD = 64, 512
+
+
+def reads_ws_bytes(n_records, n_samples):
+    return 16 * n_records * n_samples + 16 * n_records + 16
+
+
+class ReadsIn(C.Structure):
+    _fields_ = [('text', C.c_void_p), ('n_bytes', C.c_int64), ('n_records', C.c_int32), ('n_samples', C.c_int32),
+                ('smp_off', C.c_void_p), ('line_end', C.c_void_p), ('read_idx', C.c_void_p), ('period', C.c_void_p),
+                ('gt', C.c_void_p), ('allele_off', C.c_void_p), ('allele_bp', C.c_void_p)]
+
+
+class ReadsOut(C.Structure):
+    _fields_ = [('read_off', C.c_void_p), ('flags', C.c_void_p), ('workspace', C.c_void_p), ('read_val', C.c_void_p),
+                ('read_cnt', C.c_void_p), ('ab', C.c_void_p)]
+
+
 FORMAT_MAX_FIELDS, FORMAT_MAX_FILTERS = 16, 7
 
 
@@ -225,7 +244,7 @@ EXPORTS = [
     'trk_locus_stats', 'trk_locus_finalize', 'trk_call_filters', 'trk_locus_filters',
     'trk_comm_unique_id', 'trk_comm_init', 'trk_allreduce_sum_i64', 'trk_allgather',
     'trk_binomtest_two_sided', 'trk_binom_pmf', 'trk_binomtest_batch', 'trk_synth_fill', 'trk_synth_fill_gangstr', 'trk_test_set_option', 'trk_test_get_option',
-    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_mosaic_fit', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
+    'trk_assoc_scan', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_mosaic_fit', 'trk_parse_reads', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
     'trk_host_alloc', 'trk_host_free', 'trk_memcpy_h2d_async', 'trk_memcpy_d2h_async', 'trk_queue_sync', 'trk_thread_queue', 'trk_exchange', 'trk_event_record', 'trk_event_wait',
 ]
 
@@ -238,7 +257,7 @@ class TrkError(RuntimeError):
 
 # the sources libtrk.so is built from, in the order csrc/Makefile hashes them
 _SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_binom.h', 'csrc/trk_compare.hip', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
-            'csrc/trk_mosaic.hip', 'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
+            'csrc/trk_mosaic.hip', 'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_reads.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
 
 
 def source_digest():
@@ -392,6 +411,7 @@ def load():
     lib.trk_compare.argtypes = [vp, P(CompareIn), P(CompareOut)]
     lib.trk_mosaic_fit.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int32] + [vp] * 7
     lib.trk_parse_samples.argtypes = [vp, P(ParseIn), P(ParseOut)]
+    lib.trk_parse_reads.argtypes = [vp, P(ReadsIn), P(ReadsOut), C.c_int]
     lib.trk_inflate_blocks.argtypes = [vp, P(InflateIn), P(InflateOut)]
     lib.trk_inflate_hook.argtypes = [vp, P(vp), P(vp), P(vp)]
     lib.trk_inflate_text.argtypes = [vp, u64, i64, vp, u64]

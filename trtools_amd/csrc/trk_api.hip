@@ -1007,6 +1007,40 @@ int trk_parse_samples(trk_ctx* ctx, const trk_parse_in* in, trk_parse_out* out) 
     return TRK_OK;
 }
 
+int trk_parse_reads(trk_ctx* ctx, const trk_reads_in* in, const trk_reads_out* out, int pass) {
+    if (!ctx) return TRK_ERR_ARG;
+    if (!in || !out || (pass != 1 && pass != 2)) return fail(ctx, TRK_ERR_ARG, "parse_reads: arguments are NULL, or pass %d", pass);
+    if (in->n_records < 0 || in->n_samples < 0 || (int64_t)in->n_records * in->n_samples >= INT32_MAX)
+        return fail(ctx, TRK_ERR_ARG, "parse_reads: records %d, samples %d (calls are indexed in int32)", in->n_records, in->n_samples);
+    if (!out->read_off || !out->flags) return fail(ctx, TRK_ERR_ARG, "parse_reads: read_off and flags are required");
+    (void)hipSetDevice(ctx->device);
+    if (in->n_records == 0 || in->n_samples == 0) {
+        if (pass == 1) {
+            HIPCHK(ctx, hipMemsetAsync(out->read_off, 0, sizeof(int32_t), ctx->s()));
+            if (in->n_records > 0) HIPCHK(ctx, hipMemsetAsync(out->flags, 0, (size_t)in->n_records, ctx->s()));
+        }
+        return TRK_OK;
+    }
+    if (!in->text || ((uintptr_t)in->text & 15u) || !in->smp_off || !in->line_end || !in->read_idx || !in->period ||
+        !out->workspace || ((uintptr_t)out->workspace & 7u))
+        return fail(ctx, TRK_ERR_ARG, "parse_reads: text (16-byte aligned), offsets, read_idx, period and the workspace are required");
+    const int n_gt = (in->gt != nullptr) + (in->allele_off != nullptr) + (in->allele_bp != nullptr);
+    if (n_gt != 0 && n_gt != 3) return fail(ctx, TRK_ERR_ARG, "parse_reads: gt, allele_off and allele_bp come together");
+    if (pass == 2 && n_gt == 3 && !out->ab) return fail(ctx, TRK_ERR_ARG, "parse_reads: ab is NULL");
+    int64_t* total_dev = nullptr;
+    if (pass == 2) {
+        // (read_val / read_cnt may be NULL when there is no entry at all: nothing is stored then)
+        HIPCHK(ctx, trk::launch_parse_reads(*in, *out, 2, ctx->s(), &total_dev));
+        return TRK_OK;
+    }
+    HIPCHK(ctx, trk::launch_parse_reads(*in, *out, 1, ctx->s(), &total_dev));
+    int64_t total = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&total, total_dev, sizeof total, hipMemcpyDeviceToHost, ctx->s()));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->s()));
+    if (total > INT32_MAX) return fail(ctx, TRK_ERR_DATA, "parse_reads: %lld entries, more than int32 offsets hold", (long long)total);
+    return TRK_OK;
+}
+
 int trk_inflate_blocks(trk_ctx* ctx, const trk_inflate_in* in, const trk_inflate_out* out) {
     if (!ctx) return TRK_ERR_ARG;
     if (!in || !out) return fail(ctx, TRK_ERR_ARG, "inflate_blocks: arguments are NULL");

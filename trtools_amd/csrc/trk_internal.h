@@ -137,5 +137,8 @@ hipError_t launch_scan_u32(uint32_t* counts, int n, uint32_t* total, hipStream_t
 
 hipError_t launch_parse_samples(const trk_parse_in& in, const trk_parse_out& out, hipStream_t stream);
 hipError_t launch_format_samples(const trk_format_in& in, const trk_format_out& out, int pass, hipStream_t stream);
+// prancSTR's read vectors (trk_reads.hip); pass 1 leaves at *total_dev where the number of entries stands as an int64
+hipError_t launch_parse_reads(const trk_reads_in& in, const trk_reads_out& out, int pass, hipStream_t stream,
+                              int64_t** total_dev);
 }  // namespace trk
 #endif

@@ -1001,6 +1001,59 @@ class Engine:
                 text_d.free()
         return out
 
+    def parse_reads(self, text, smp_off, line_end, n_samples, read_idx, period, gt=None, allele_off=None,
+                    allele_bp=None):
+        """trk_parse_reads (include/trk.h): the read vectors ('bp|count;...', HipSTR's MALLREADS) of L records parsed on
+        the device into what ``mosaic_fit`` reads.  text / smp_off / line_end as for ``parse_samples``; read_idx int8
+        [L]: index of the field among the record's FORMAT keys (-1: absent); period int32 [L].  With gt int16
+        [L, S, 2] (``parse_samples``' genotypes), allele_off int32 [L + 1] and allele_bp int32 [sumA] (allele length
+        minus reference length, in bp) also ab int32 [L, S, 2] in repeat units.  Every entry a host array or a
+        DeviceArray.  Both passes and the one 4-byte download between them.  Returns a dict of DeviceArrays: read_off
+        int32 [L*S + 1], read_val, read_cnt int32, flags uint8 [L] (0, or _lib.PARSE_* bits: a flagged record has no
+        reads and no genotypes here -- parse it on the host) and ab (None without gt)."""
+        if (gt is None) != (allele_off is None) or (gt is None) != (allele_bp is None):
+            raise ValueError("parse_reads: gt, allele_off and allele_bp come together")
+        tmp = []
+
+        def dev(x, dt):
+            if isinstance(x, DeviceArray):
+                return x
+            d = self.upload(np.ascontiguousarray(x, dtype=dt), dt)
+            tmp.append(d)
+            return d
+        if isinstance(text, DeviceArray):
+            text_d = text
+        else:
+            host = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text.view(np.uint8).reshape(-1)
+            text_d = self.empty((host.shape[0] + 32,), np.uint8)
+            tmp.append(text_d)
+            if host.shape[0]:
+                self._chk(self.lib.trk_memcpy_h2d(self.ctx, text_d.ptr, host.ctypes.data, host.shape[0]))
+        n_rec, ns = int(np.prod(smp_off.shape)) if isinstance(smp_off, DeviceArray) else int(np.size(smp_off)), int(n_samples)
+        rin = L.ReadsIn()
+        rin.text, rin.n_bytes, rin.n_records, rin.n_samples = text_d.ptr, text_d.nbytes, n_rec, ns
+        rin.smp_off, rin.line_end = dev(smp_off, np.int64).ptr, dev(line_end, np.int64).ptr
+        rin.read_idx, rin.period = dev(read_idx, np.int8).ptr, dev(period, np.int32).ptr
+        out = dict(read_off=self.empty((n_rec * ns + 1,), np.int32), flags=self.empty((n_rec,), np.uint8), ab=None)
+        if gt is not None:
+            if tuple(gt.shape) != (n_rec, ns, 2):
+                raise ValueError("parse_reads: gt is [L, S, 2]")
+            rin.gt, rin.allele_off, rin.allele_bp = dev(gt, np.int16).ptr, dev(allele_off, np.int32).ptr, dev(allele_bp, np.int32).ptr
+            out['ab'] = self.empty((n_rec, ns, 2), np.int32)
+        ws = self.empty((L.reads_ws_bytes(n_rec, ns),), np.uint8)
+        tmp.append(ws)
+        rout = L.ReadsOut(out['read_off'].ptr, out['flags'].ptr, ws.ptr, None, None, out['ab'].ptr if gt is not None else None)
+        self._chk(self.lib.trk_parse_reads(self.ctx, C.byref(rin), C.byref(rout), 1))
+        n_ent = int(out['read_off'].get_rows(n_rec * ns, n_rec * ns + 1)[0])
+        out['read_val'], out['read_cnt'] = self.empty((n_ent,), np.int32), self.empty((n_ent,), np.int32)
+        rout.read_val, rout.read_cnt = out['read_val'].ptr, out['read_cnt'].ptr
+        self._chk(self.lib.trk_parse_reads(self.ctx, C.byref(rin), C.byref(rout), 2))
+        self.sync()                           # (the temporaries go back to the pool: the kernels must be done with them)
+        with self.idle_frees():
+            for t in tmp:
+                t.free()
+        return out
+
     def qc_reduce(self, batch, quality=None, sample_in=None, ignore_no_call=False):
         """trk_qc_reduce (qcSTR's reductions, include/trk.h): per-sample and per-locus call counts, and with a
         quality plane (float32 [L, S], host or device) the quality sums and the numbers of entries summed.

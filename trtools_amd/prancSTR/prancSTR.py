@@ -193,3 +193,116 @@ def mosaic_fit_records(records, readfield='MALLREADS', samples=None, output_all=
         out[k] = v.get()
         v.free()
     return out
+
+
+_FIT_KEYS = ('C', 'support', 'f', 'pval', 'll_fit', 'll_null', 'status')
+
+
+def _batch_tables(rb, hz, readfield):
+    """What trk_parse_reads and the fit need of a raw batch beside its text, from the heads of the lines and the
+    harmoniser's tables -- per RECORD, nothing per call: (chrom, id, read_idx int8 [L], gt_idx, stutter [L, 3],
+    allele_bp int32 [sumA])."""
+    chrom, ids, ridx, stutter, keys_of = [], [], [], [], {}
+    for l in range(rb.n):
+        head = rb.head_fields(l)
+        chrom.append(head[0])
+        ids.append(head[2])
+        fmt = head[8] if len(head) > 8 else ''
+        if fmt not in keys_of:
+            keys = fmt.split(':')
+            keys_of[fmt] = keys.index(readfield) if readfield in keys and keys.index(readfield) < 128 else -1
+        ridx.append(keys_of[fmt])
+        info = dict(item.split('=', 1) for item in head[7].split(';') if item.startswith('INFRAME_') and '=' in item)
+        stutter.append(stutter_triple({k: float(v) for k, v in info.items()}))
+    # an allele's length in bp is the length of its harmonised sequence: key str_class[allele] of its locus
+    first = np.repeat(hz.allele_off[:-1], np.diff(hz.allele_off)).astype(np.int64)
+    at = first + hz.str_class
+    bp = (hz.key_off[at + 1] - hz.key_off[at]).astype(np.int64)
+    ref = first + hz.str_class[first] if first.size else first
+    bp -= hz.key_off[ref + 1] - hz.key_off[ref]
+    return chrom, ids, np.array(ridx, dtype=np.int8), np.array(stutter, dtype=np.float64).reshape(rb.n, 3), bp.astype(np.int32)
+
+
+def _splice(out, rows, sub):
+    """The rows ``rows`` of the batch's result ``out`` replaced by the rows of ``sub`` (mosaic_fit_records of those
+    records): dense arrays row by row, the CSR arrays record by record."""
+    nl, ns = out['ab'].shape[:2]
+    for k in _FIT_KEYS + ('ab', 'stutter'):
+        out[k][rows] = sub[k]
+    cut = out['read_off'][::ns] if ns else out['read_off']
+    scut = sub['read_off'][::ns] if ns else sub['read_off']
+    vals = [out['read_val'][cut[l]:cut[l + 1]] for l in range(nl)]
+    cnts = [out['read_cnt'][cut[l]:cut[l + 1]] for l in range(nl)]
+    per_call = np.diff(out['read_off']).reshape(nl, ns)
+    for j, l in enumerate(rows):
+        vals[l], cnts[l] = sub['read_val'][scut[j]:scut[j + 1]], sub['read_cnt'][scut[j]:scut[j + 1]]
+        per_call[l] = np.diff(sub['read_off'])[j * ns:(j + 1) * ns]
+    out['read_val'] = np.concatenate(vals + [np.empty(0, np.int32)]).astype(np.int32)
+    out['read_cnt'] = np.concatenate(cnts + [np.empty(0, np.int32)]).astype(np.int32)
+    out['read_off'] = np.concatenate([[0], np.cumsum(per_call.reshape(-1))]).astype(np.int32)
+
+
+def mosaic_fit_vcf(path, readfield='MALLREADS', samples=None, output_all=False, batch_records=1024, engine=None):
+    """The mosaic fit of every call of a HipSTR VCF, a batch of records at a time, with no Python object per call:
+    native reader -> native harmoniser -> the text on the device -> trk_parse_samples (genotypes) -> trk_parse_reads
+    (ab and the read vectors) -> trk_mosaic_fit.  A generator: per batch ``mosaic_fit_records``' dict of host arrays
+    without ``reads``, ``q`` and ``dp``, plus ``chrom``, ``pos`` (TRRecord.pos) and ``id`` of the records.  ``samples``: the columns to
+    report (indices; None: all).  Records the native harmoniser leaves to Python, records either device parser flags and
+    batches of another ploidy than two go through the record objects and ``mosaic_fit_records``; their rows are put in
+    place."""
+    from .. import vcfnative
+    from ..utils import tr_harmonizer as trh
+    eng = _engine(engine)
+    reader = vcfnative.NativeVCFReader(path, batch_records=batch_records)
+    reader.device_parse(eng)
+    cols = None if samples is None else [int(s) for s in samples]
+    try:
+        while True:
+            rb = reader.read_raw_batch(batch_records)
+            if rb.n == 0:
+                break
+            try:
+                nl, ns = rb.n, reader.n_samples
+                hz = rb.harmonize('hipstr')
+                chrom, ids, ridx, stutter, allele_bp = _batch_tables(rb, hz, readfield)
+                host = np.asarray(hz.status) != 0
+                d = rb.dev
+                if d is None or d['gt'].shape[2] != 2:
+                    host[:] = True
+                out = dict(chrom=chrom, id=ids, pos=np.array(hz.tr_pos, dtype=np.int64), stutter=stutter)
+                if not host.all():
+                    ridx[host] = -1
+                    pr = eng.parse_reads(d['text'], d['smp_off'], d['line_end'], ns, ridx, np.maximum(hz.period, 1),
+                                         gt=d['gt'], allele_off=hz.allele_off, allele_bp=allele_bp)
+                    flags = pr.pop('flags')
+                    host |= flags.get() != 0
+                    flags.free()
+                    res = eng.mosaic_fit(pr['ab'], pr['read_off'], pr['read_val'], pr['read_cnt'], stutter,
+                                         output_all=output_all)
+                    for k, v in list(pr.items()) + list(res.items()):
+                        out[k] = v.get()
+                        v.free()
+                else:
+                    out.update(ab=np.empty((nl, ns, 2), np.int32), read_off=np.zeros(nl * ns + 1, np.int32),
+                               read_val=np.empty(0, np.int32), read_cnt=np.empty(0, np.int32))
+                    out.update({k: np.empty((nl, ns), dt) for k, dt in zip(
+                        _FIT_KEYS, (np.int32, np.int32, np.float64, np.float64, np.float64, np.float64, np.uint8))})
+                if host.any():
+                    rows = np.flatnonzero(host)
+                    recs = rb.records()
+                    trs = [trh.HarmonizeRecord(trh.VcfTypes.hipstr, recs[l]) for l in rows]
+                    _splice(out, rows, mosaic_fit_records(trs, readfield=readfield, output_all=output_all, engine=eng))
+                    out['pos'][rows] = [tr.pos for tr in trs]
+                if cols is not None:
+                    cnt = np.diff(out['read_off']).reshape(nl, ns)[:, cols].reshape(-1)
+                    src = np.repeat(out['read_off'][:-1].reshape(nl, ns)[:, cols].reshape(-1), cnt)
+                    new_off = np.concatenate([[0], np.cumsum(cnt)])
+                    src = src + np.arange(src.size) - np.repeat(new_off[:-1], cnt)
+                    out.update(read_off=new_off.astype(np.int32), read_val=out['read_val'][src], read_cnt=out['read_cnt'][src])
+                    for k in _FIT_KEYS + ('ab',):
+                        out[k] = np.ascontiguousarray(out[k][:, cols])
+                yield out
+            finally:
+                rb.release_device()
+    finally:
+        reader.close()
