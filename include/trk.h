@@ -511,6 +511,29 @@ typedef struct {
 } trk_assoc_out;
 int trk_assoc_scan(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out);
 
+/* T outcomes against the same covariates in ONE pass over the genotype tensor (a phenome-wide run: T traits of one
+ * cohort).  prm->vec is [T + K, S]: rows 0..T-1 the standardised outcomes, rows T.. the K covariates; n_vec = T + K.
+ * The scan is trk_assoc_scan's over T + K rows (same kernels, same choice among them); then one wavefront per locus
+ * factors the normal matrix of [1, covariates, genotype] ONCE and carries the T right-hand sides through the
+ * factorisation, one per lane, so T + K <= TRK_ASSOC_MAX_MULTI (more is TRK_ERR_ARG).
+ *   out           as trk_assoc_scan fills it for a run on [outcome, covariates]: every count, filter and status is a
+ *                 property of the locus and the design, not of the outcome -- 'n covars >= n samples' and the rank
+ *                 count 1 + K + 1 columns, never T.  PVAL / COEF / SE / RSQUARED / TVALUE hold outcome 0's values.
+ *   outcome_f64   device [L, T, TRK_AO_COLS]; nan where the locus is not tested (status != TRK_AS_OK).
+ * A sample is in or out for every outcome alike (sample_in); there is no per-outcome missingness.
+ * n_outcomes == 1 runs trk_assoc_scan itself and copies its five columns to outcome_f64. */
+#define TRK_ASSOC_MAX_MULTI 62
+enum {
+    TRK_AO_PVAL = 0,
+    TRK_AO_COEF = 1,      /* coefficient of the STANDARDISED genotype, as TRK_AF_COEF */
+    TRK_AO_SE = 2,
+    TRK_AO_RSQUARED = 3,
+    TRK_AO_TVALUE = 4,
+    TRK_AO_COLS = 5
+};
+int trk_assoc_scan_multi(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, int32_t n_outcomes,
+                         trk_assoc_out* out, double* outcome_f64);
+
 /* associaTR --beagle-dosages (load_and_filter_genotypes.py:179-215, associaTR.py:266-273): the
  * regressor is the expected summed length from the Beagle AP1/AP2 allele probabilities,
  *     g_s = sum over rounded-length classes u (ascending) of len_u * (d_u,1 + d_u,2),

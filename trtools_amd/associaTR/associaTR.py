@@ -64,10 +64,12 @@ def _weighted_binom_conf(weights, successes, confidence):
     return (phat, center - half, center + half)
 
 
-def _load_design(all_samples, trait_fnames, same_samples, sample_fname):
+def _load_design(all_samples, trait_fnames, same_samples, sample_fname, n_outcomes=1):
     """Covariate assembly of perform_gwas_helper (associaTR.py:138-204), messages included.
     Returns (sample_filter bool[S], covars [Sf, 1+T] with column 0 reserved for the genotype and
-    column 1 the intercept, outcome [Sf], pheno_std)."""
+    column 1 the intercept, outcome [Sf], pheno_std).  ``n_outcomes`` > 1 (--n-outcomes): the first n_outcomes trait
+    columns are outcomes -- outcome [Sf, n_outcomes], pheno_std [n_outcomes], each outcome standardised by itself --
+    and covars holds the intercept and the remaining columns, as a single-outcome run with these covariates has it."""
     print('{} samples in the VCF'.format(len(all_samples)), flush=True)
     if not same_samples:
         covars = np.load(trait_fnames[0])
@@ -113,6 +115,16 @@ def _load_design(all_samples, trait_fnames, same_samples, sample_fname):
            ).format(before - after, after))
 
     covars = covars[sample_filter, :]
+    if n_outcomes > 1:
+        if covars.shape[1] - 1 < n_outcomes:
+            raise ValueError("associaTR: --n-outcomes %d, but the traits hold %d columns" % (n_outcomes, covars.shape[1] - 1))
+        # (column by column: the very call a single-outcome run makes, to the last bit)
+        pheno_std = np.array([np.std(covars[:, 1 + t]) for t in range(n_outcomes)])
+        covars = (covars - np.mean(covars, axis=0)) / np.std(covars, axis=0)
+        outcome = covars[:, 1:1 + n_outcomes].copy()
+        covars = np.delete(covars, np.s_[2:1 + n_outcomes], axis=1)
+        covars[:, 1] = 1
+        return sample_filter, covars, outcome, pheno_std
     pheno_std = np.std(covars[:, 1])
     covars = (covars - np.mean(covars, axis=0)) / np.std(covars, axis=0)
     outcome = covars[:, 1].copy()
@@ -124,16 +136,18 @@ def _device_vectors(sample_filter, covars, outcome, beagle_dosages=False):
     """[M, S] float64 for trk_assoc_params.vec: row 0 the outcome, rows 1.. the covariates; samples
     outside the regression set hold zeros (ignored on the device).  Up to 62 rows are scanned in one
     pass, up to 126 as pairs of row groups (trk.h TRK_ASSOC_MAX_VEC_WIDE); --beagle-dosages: pairs of row groups
-    from 32 rows on."""
-    S, M = len(sample_filter), covars.shape[1] - 1
-    limit = L.ASSOC_MAX_VEC_WIDE
+    from 32 rows on.  A two-dimensional ``outcome`` [Sf, T] (--n-outcomes): rows 0..T-1 the outcomes, then the
+    covariates, at most ASSOC_MAX_MULTI rows (trk_assoc_scan_multi)."""
+    T = 1 if outcome.ndim == 1 else outcome.shape[1]
+    S, M = len(sample_filter), covars.shape[1] - 2 + T
+    limit = L.ASSOC_MAX_VEC_WIDE if T == 1 else L.ASSOC_MAX_MULTI
     if M > limit:
-        raise ValueError("associaTR: %d trait columns (phenotype + covariates); this build scans at most %d"
-                         % (M, limit))
+        raise ValueError("associaTR: %d trait columns (phenotype%s + covariates); this build scans at most %d"
+                         % (M, '' if T == 1 else 's', limit))
     vec = np.zeros((M, S), dtype=np.float64)
-    vec[0, sample_filter] = outcome
-    for k in range(1, M):
-        vec[k, sample_filter] = covars[:, 1 + k]
+    vec[0:T, sample_filter] = outcome.reshape(-1, T).T
+    for k in range(T, M):
+        vec[k, sample_filter] = covars[:, 2 + k - T]
     return vec
 
 
@@ -305,13 +319,55 @@ def _write_rows(outfile, recs, allele_off, allele_lens, res, pheno_std, non_majo
         outfile.flush()
 
 
+class _MultiOut:
+    """--n-outcomes T: one table per outcome.  T sharded outputs driven in step -- the same batches belong to this rank
+    in every one of them -- so that each table is merged exactly as a single-outcome run's is."""
+
+    def __init__(self, outfiles):
+        from ..statSTR.statSTR import _ShardedOut
+        self.outs = [_ShardedOut(f) for f in outfiles]
+        self.world = self.outs[0].world
+
+    def attach(self, reader, region=None):
+        cut = self.outs[0].attach(reader, region)
+        for o in self.outs[1:]:
+            o.contiguous = cut
+        return cut
+
+    def next_batch(self):
+        return [o.next_batch() for o in self.outs][0]
+
+    def end_batch(self):
+        for o in self.outs:
+            o.end_batch()
+
+    def finish(self):
+        for o in self.outs:
+            o.finish()
+
+
+def _write_outcome_rows(out, recs, allele_off, allele_lens, res, per, pheno_std, non_major_cutoff):
+    """The rows of one batch of a --n-outcomes run: ``res`` / ``per`` what assoc_multi_batch returned; table t gets the
+    per-locus columns with outcome t's five regression columns, rescaled by that outcome's pheno_std."""
+    from ..compute import AssocHost
+    for t, sink in enumerate(out.outs):
+        lf = res.locus_f64.copy()
+        lf[:, [L.AF_PVAL, L.AF_COEF, L.AF_SE, L.AF_RSQUARED, L.AF_TVALUE]] = per[:, t, :]
+        _write_rows(sink, recs, allele_off, allele_lens, AssocHost(res.locus_int, lf, res.allele_count), pheno_std[t],
+                    non_major_cutoff)
+
+
 def _flush(records, outfile, vec, sample_filter, pheno_std, non_major_cutoff, beagle_dosages=False):
     """One device batch of record objects -> output rows."""
     if not records:
         return
     lf_mod = load_and_filter_genotypes
     hb = pack_records(records)
-    if beagle_dosages:
+    if isinstance(outfile, _MultiOut):
+        res, per = runtime.get_compute().assoc_multi_batch(hb, vec, len(outfile.outs), sample_filter, non_major_cutoff,
+                                                           precision=lf_mod.allele_len_precision)
+        _write_outcome_rows(outfile, records, hb.allele_off, hb.allele_lens, res, per, pheno_std, non_major_cutoff)
+    elif beagle_dosages:
         from ..batch import stack_plane
         ap1 = stack_plane([np.asarray(r.format['AP1'], dtype=np.float32) for r in records], np.float32)
         ap2 = stack_plane([np.asarray(r.format['AP2'], dtype=np.float32) for r in records], np.float32)
@@ -398,7 +454,11 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
                                    hz.len_class_value, lists=hz.lists)
         tables = assoc_tables_from_classes(hz.allele_off, hz.allele_len, hz.len_class_value, hz.n_len_classes,
                                            lf_mod.allele_len_precision)
-        if getattr(compute, 'eng', None) is not None:
+        per = None
+        if isinstance(shard, _MultiOut):
+            res, per = compute.assoc_multi_batch(hb, vec, len(shard.outs), sample_filter, non_major_cutoff,
+                                                 precision=lf_mod.allele_len_precision, tables=tables)
+        elif getattr(compute, 'eng', None) is not None:
             res = compute.assoc_batch(hb, vec, sample_filter, non_major_cutoff, precision=lf_mod.allele_len_precision,
                                       tables=tables)
         else:                                     # (the tests' stand-in computes from the per-locus lists)
@@ -411,7 +471,10 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
         chroms, poss, motifs = rb.chrom_column(), hz.tr_pos.tolist(), rb.motifs(hz, vcftype.name)
         lens = [alen[off[l]:off[l + 1]] for l in range(rb.n)]
         facts = [_Facts(chroms[l], poss[l], motifs[l], lens[l]) for l in range(rb.n)]
-        _write_rows(shard, facts, off, lens, res, pheno_std, non_major_cutoff)
+        if per is not None:
+            _write_outcome_rows(shard, facts, off, lens, res, per, pheno_std, non_major_cutoff)
+        else:
+            _write_rows(shard, facts, off, lens, res, pheno_std, non_major_cutoff)
         shard.end_batch()
     if last_rb is not None:
         last_rb.release_device()
@@ -419,27 +482,31 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
 
 
 def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait_fnames, same_samples, sample_fname,
-                        non_major_cutoff, beagle_dosages=False, attach=None):
-    """Header, covariates, batched scan (associaTR.py:117-372 without the plotting statistics)."""
+                        non_major_cutoff, beagle_dosages=False, attach=None, n_outcomes=1):
+    """Header, covariates, batched scan (associaTR.py:117-372 without the plotting statistics).  ``n_outcomes`` > 1:
+    ``outfile`` is a list of n_outcomes open files and ``phenotype_name`` their comma-separated names, one table each."""
     from .. import dist
     rank = dist.get_comm()[0]
+    tables = [(outfile, phenotype_name)] if n_outcomes == 1 else list(zip(outfile, phenotype_name.split(',')))
     if rank == 0:
-        outfile.write("chrom\tpos\talleles\tn_samples_tested\tlocus_filtered\tp_{}\tcoeff_{}\t".format(
-            phenotype_name, phenotype_name))
-        outfile.write('se_{}\tregression_R^2\t'.format(phenotype_name))
-        outfile.flush()
-    sample_filter, covars, outcome, pheno_std = _load_design(all_samples, trait_fnames, same_samples, sample_fname)
+        for f, name in tables:
+            f.write("chrom\tpos\talleles\tn_samples_tested\tlocus_filtered\tp_{}\tcoeff_{}\t".format(name, name))
+            f.write('se_{}\tregression_R^2\t'.format(name))
+            f.flush()
+    sample_filter, covars, outcome, pheno_std = _load_design(all_samples, trait_fnames, same_samples, sample_fname,
+                                                             n_outcomes)
     vec = _device_vectors(sample_filter, covars, outcome, beagle_dosages)
     if rank == 0:
         fields = list(load_and_filter_genotypes.DETAIL_FIELDS)
         if beagle_dosages:
             fields.extend(load_and_filter_genotypes.DOSAGE_DETAIL_FIELDS)
-        outfile.write('\t'.join(fields) + '\n')
+        for f, _ in tables:
+            f.write('\t'.join(fields) + '\n')
 
     # one process per GPU (WORLD_SIZE > 1): every rank scans its contiguous share of the records (or, where the input
     # cannot be cut, batch b mod WORLD_SIZE); rank 0 writes the merged table (statSTR._ShardedOut)
     from ..statSTR.statSTR import _ShardedOut
-    shard = _ShardedOut(outfile)
+    shard = _ShardedOut(outfile) if n_outcomes == 1 else _MultiOut(outfile)
     if attach is not None:
         attach['shard'] = shard        # iter_records cuts the reader into contiguous shards when it starts
     batch_loci = max(1, min(4096, BATCH_CELLS // max(1, len(all_samples))))
@@ -477,10 +544,23 @@ def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait
 
 def perform_gwas(outfname, tr_vcf, phenotype_name, traits_fnames, vcftype, same_samples, sample_fname, region,
                  non_major_cutoff, beagle_dosages, plotting_phenotype_fname, paired_genotype_plot,
-                 plot_phenotype_residuals, plotting_ci_alphas, imputed_ukb_strs_paper_period_check):
-    """Signature of the reference (associaTR.py:432-482)."""
+                 plot_phenotype_residuals, plotting_ci_alphas, imputed_ukb_strs_paper_period_check, n_outcomes=1):
+    """Signature of the reference (associaTR.py:432-482), plus ``n_outcomes`` (--n-outcomes T): the first T trait
+    columns are outcomes regressed on the same covariates in one pass over the genotypes, ``phenotype_name`` their T
+    comma-separated names, and table t is written to ``<outfname>.<name t>``."""
     if plotting_phenotype_fname or paired_genotype_plot or plot_phenotype_residuals or plotting_ci_alphas:
         raise NotImplementedError("the hidden --plotting-phenotype options of the reference are not provided")
+    n_outcomes = int(n_outcomes)
+    names = phenotype_name.split(',')
+    if n_outcomes < 1:
+        raise ValueError("--n-outcomes must be at least 1")
+    if n_outcomes > 1:
+        if beagle_dosages:
+            raise ValueError("--n-outcomes %d with --beagle-dosages: the dosage scan regresses one outcome per run"
+                             % n_outcomes)
+        if len(names) != n_outcomes or len(set(names)) != n_outcomes or not all(names):
+            raise ValueError("--n-outcomes %d needs %d distinct comma-separated names in phenotype_name, got %r"
+                             % (n_outcomes, n_outcomes, phenotype_name))
     reader = utils.LoadSingleReader(tr_vcf, checkgz=False)
     if reader is None:
         raise ValueError("could not open %s" % tr_vcf)
@@ -495,6 +575,23 @@ def perform_gwas(outfname, tr_vcf, phenotype_name, traits_fnames, vcftype, same_
             tr_vcf, region, vcftype, beagle_dosages, imputed_ukb_strs_paper_period_check, attach=attach)
     from .. import dist
     rank = dist.get_comm()[0]
+    if n_outcomes > 1:
+        import contextlib
+        import os
+        finals = ['%s.%s' % (outfname, name) for name in names]
+        temps = [f + ('.temp' if rank == 0 else '.rank%d.temp' % rank) for f in finals]
+        print("Writing output to {}".format(', '.join(f + '.temp' for f in finals)), flush=True)
+        with contextlib.ExitStack() as stack:
+            outfiles = [stack.enter_context(open(t, 'w')) for t in temps]
+            perform_gwas_helper(outfiles, all_samples, record_iter, phenotype_name, traits_fnames, same_samples,
+                                sample_fname, non_major_cutoff, False, attach=attach, n_outcomes=n_outcomes)
+        for t, f in zip(temps, finals):
+            if rank != 0:
+                os.remove(t)          # only rank 0's files hold the merged tables
+            else:
+                shutil.move(t, f)
+        print("Done.", flush=True)
+        return
     temp = outfname + '.temp' if rank == 0 else outfname + '.rank%d.temp' % rank
     print("Writing output to {}.temp".format(outfname), flush=True)
     with open(temp, 'w') as outfile:
@@ -534,6 +631,12 @@ def getargs():  # pragma: no cover
     parser.add_argument('--beagle-dosages', action='store_true', default=False,
                         help="regress against Beagle dosages from the AP{1,2} fields instead of from the GT field. "
                              "(The GP field is not supported)")
+    parser.add_argument('--n-outcomes', type=int, default=1,
+                        help="Regress the first N trait columns of the first traits file, each as an outcome of its own, "
+                             "on the remaining columns (the covariates they share) in ONE pass over the genotypes. "
+                             "phenotype_name is then N comma-separated names and table i is written to "
+                             "<outfile>.<name i>; each is the table a run on that outcome alone writes. Outcomes + "
+                             "covariates: at most 62. Not with --beagle-dosages.")
     parser.add_argument('--plotting-phenotype', help=argparse.SUPPRESS)
     parser.add_argument('--paired-genotype-plot', action='store_true', default=False, help=argparse.SUPPRESS)
     parser.add_argument('--plot-phenotype-residuals', action='store_true', default=False, help=argparse.SUPPRESS)
@@ -552,7 +655,7 @@ def main(args):
     perform_gwas(args.outfile, args.tr_vcf, args.phenotype_name, args.traits, args.vcftype, args.same_samples,
                  args.sample_list, args.region, args.non_major_cutoff, args.beagle_dosages, args.plotting_phenotype,
                  args.paired_genotype_plot, args.plot_phenotype_residuals, args.plotting_ci_alphas,
-                 args.imputed_ukb_strs_paper_period_check)
+                 args.imputed_ukb_strs_paper_period_check, n_outcomes=getattr(args, 'n_outcomes', 1))
 
 
 def run():  # pragma: no cover

@@ -196,6 +196,25 @@ class DeviceCompute:
         """associaTR scan of one batch (trk_assoc_scan): vec [M, S] float64 (outcome, covariates),
         sample_in bool[S] or None; ``tables``: (allele_len, rlen_class) already made for the batch
         (synth.assoc_tables_from_classes: the batch pipeline has no per-locus Python lists).  Returns AssocHost."""
+        b, vec_d, sin_d, alen_d, rcls_d = self._assoc_inputs(hb, vec, sample_in, precision, tables)
+        res = self.eng.assoc_scan(b, vec_d, alen_d, rcls_d, sample_in=sin_d, non_major_cutoff=non_major_cutoff)
+        out = AssocHost(res.locus_int.get(), res.locus_f64.get(), res.allele_count.get())
+        self._free(b, alen_d, rcls_d, sin_d, res.locus_int, res.locus_f64, res.allele_count)
+        return out
+
+    def assoc_multi_batch(self, hb, vec, n_outcomes, sample_in, non_major_cutoff, precision=2, tables=None):
+        """associaTR scan of one batch for ``n_outcomes`` outcomes at once (trk_assoc_scan_multi): vec [T + K, S], rows
+        0..T-1 the outcomes, rows T.. their shared covariates; padding and tables as assoc_batch.  Returns (AssocHost,
+        outcome_f64 [L, T, AO_COLS] host array)."""
+        b, vec_d, sin_d, alen_d, rcls_d = self._assoc_inputs(hb, vec, sample_in, precision, tables)
+        res, per = self.eng.assoc_scan_multi(b, vec_d, n_outcomes, alen_d, rcls_d, sample_in=sin_d,
+                                             non_major_cutoff=non_major_cutoff)
+        out = (AssocHost(res.locus_int.get(), res.locus_f64.get(), res.allele_count.get()), per.get())
+        self._free(b, alen_d, rcls_d, sin_d, res.locus_int, res.locus_f64, res.allele_count, per)
+        return out
+
+    def _assoc_inputs(self, hb, vec, sample_in, precision, tables):
+        """The device batch, vector block, sample mask and allele tables of an association scan of ``hb``."""
         from .synth import pack_assoc_tables
         eng = self.eng
         b = self._upload(hb)
@@ -219,10 +238,7 @@ class DeviceCompute:
         vec_d = self._assoc_vec[1]
         sin_d = eng.upload(sin) if sin is not None else None
         alen_d, rcls_d = eng.upload(alen), eng.upload(rcls)
-        res = eng.assoc_scan(b, vec_d, alen_d, rcls_d, sample_in=sin_d, non_major_cutoff=non_major_cutoff)
-        out = AssocHost(res.locus_int.get(), res.locus_f64.get(), res.allele_count.get())
-        self._free(b, alen_d, rcls_d, sin_d, res.locus_int, res.locus_f64, res.allele_count)
-        return out
+        return b, vec_d, sin_d, alen_d, rcls_d
 
     def close(self):
         """Release what the object keeps on the device between calls."""

@@ -811,7 +811,9 @@ int trk_exchange(trk_ctx* ctx, int64_t* sums, size_t n_sums, const void* send, v
 
 // ---- scalar helpers --------------------------------------------------------------
 // ---- associaTR scan -----------------------------------------------------------------------
-int trk_assoc_scan(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out) {
+// trk_assoc_scan (n_outcomes 1, outcome_f64 null) and trk_assoc_scan_multi
+static int assoc_scan_run(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out, int n_outcomes,
+                          double* outcome_f64) {
     if (!ctx) return TRK_ERR_ARG;
     int rc = check_batch(ctx, in);
     if (rc) return rc;
@@ -837,13 +839,30 @@ int trk_assoc_scan(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* pr
     HIPCHK(ctx, trk::launch_assoc_prepare(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->s()));
     {
         ProfScope ps(ctx, TRK_K_ASSOC_SCAN);
-        HIPCHK(ctx, trk::launch_assoc_scan(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->n_cu, ctx->s()));
+        HIPCHK(ctx, trk::launch_assoc_scan(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->n_cu, ctx->s(), n_outcomes));
     }
     {
         ProfScope ps(ctx, TRK_K_ASSOC_FINALIZE);
-        HIPCHK(ctx, trk::launch_assoc_finalize(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->s()));
+        HIPCHK(ctx, trk::launch_assoc_finalize(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->s(), n_outcomes, outcome_f64));
     }
     return TRK_OK;
+}
+
+int trk_assoc_scan(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out) {
+    return assoc_scan_run(ctx, in, prm, out, 1, nullptr);
+}
+
+int trk_assoc_scan_multi(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, int32_t n_outcomes, trk_assoc_out* out,
+                         double* outcome_f64) {
+    if (!ctx) return TRK_ERR_ARG;
+    if (!prm) return fail(ctx, TRK_ERR_ARG, "assoc params/outputs are NULL");
+    if (n_outcomes < 1 || n_outcomes > prm->n_vec)
+        return fail(ctx, TRK_ERR_ARG, "n_outcomes %d outside [1, n_vec = %d]", (int)n_outcomes, (int)prm->n_vec);
+    if (n_outcomes > 1 && prm->n_vec > TRK_ASSOC_MAX_MULTI)
+        return fail(ctx, TRK_ERR_ARG, "%d outcomes + %d covariates: trk_assoc_scan_multi takes at most %d rows (one row of the "
+                    "locus's tile per lane)", (int)n_outcomes, (int)(prm->n_vec - n_outcomes), TRK_ASSOC_MAX_MULTI);
+    if (!outcome_f64 && in && in->n_loci > 0) return fail(ctx, TRK_ERR_ARG, "assoc outputs are NULL");
+    return assoc_scan_run(ctx, in, prm, out, n_outcomes, outcome_f64);
 }
 
 int trk_assoc_scan_dosage(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, const trk_assoc_dosage* dos,

@@ -23,6 +23,8 @@
 //                     that the cutoff comparison is bit-exact), Cholesky with the genotype
 //                     column last (beta = z_p / L_pp, var = scale / L_pp^2, ssr = y'y - |z|^2),
 //                     two-sided t tail (trk_student.h).
+//   k_assoc_regress_multi  trk_assoc_scan_multi: T outcomes x the same covariates from ONE scan over T + K rows and
+//                     one factorisation per locus (wave per locus, the T right-hand sides one per lane).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -83,6 +85,7 @@ struct AssocArgs {
     unsigned long long* missbits;   // [L][nsteps][4]: word (step, j), bit `lane` <-> sample 256 step + 4 lane + j
     double* vect;                   // [S][16 RT] sample-major copy of the vector block (+ the row of ones, zero rows)
     int nsteps;
+    int n_out;                      // outcome rows at the head of vec (1: trk_assoc_scan; T: trk_assoc_scan_multi)
 };
 
 // -------------------------------------------------------------------------------------------
@@ -1071,7 +1074,11 @@ template <int RT> struct GmCfg {
     static constexpr int GROUP = GM_GROUP_ALL;    // batches of four samples per software-pipeline stage
     static constexpr bool TWO = RT == 1;            // a second accumulator set (one tile pair: consecutive products
 };                                                  // would wait for each other)
-template <int RT>
+// TO: the multi-outcome form (trk_assoc_scan_multi: rows 0..n_out-1 of the block are outcomes, and nobody reads the
+// product of two different outcomes).  TO >= 0: entries (ra, rb) with ra < rb < n_out are not written -- at 52 outcomes
+// + 10 covariates 1326 of the record's 2016 entries -- and the tile pairs (ti, tj), ti < tj < TO, that hold nothing
+// else (TO = whole 16-row tiles of outcomes) are not multiplied.  TO = -1: every entry, as the single-outcome scan wants.
+template <int RT, int TO = -1>
 __global__ __launch_bounds__(WAVE* GM_WAVES) void k_assoc_gram_miss(const AssocArgs a) {
     extern __shared__ unsigned long long gm_lds[];
     constexpr int ROWS = 16 * RT;
@@ -1111,6 +1118,10 @@ __global__ __launch_bounds__(WAVE* GM_WAVES) void k_assoc_gram_miss(const AssocA
             for (int ti = 0; ti < RT; ++ti)
 #pragma unroll
                 for (int tj = ti; tj < RT; ++tj) {
+                    if (ti < tj && tj < TO) {   // outcome x outcome only: never read
+                        ++p;
+                        continue;
+                    }
                     if (TWO && (u & 1)) Gd[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[u][ti], z[u][tj], Gd[p], 0, 0, 0);
                     else Gc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[u][ti], z[u][tj], Gc[p], 0, 0, 0);
                     ++p;
@@ -1189,6 +1200,7 @@ __global__ __launch_bounds__(WAVE* GM_WAVES) void k_assoc_gram_miss(const AssocA
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ra = 16 * ti + 4 * r + (lane >> 4), rb = 16 * tj + (lane & 15);
+                if (TO >= 0 && ra < rb && rb < a.n_out) continue;
                 if (ra <= rb && rb <= M) rec[3 + M + ra * (M + 1) - ra * (ra - 1) / 2 + (rb - ra)] = Gc[p][r];
             }
             ++p;
@@ -1869,7 +1881,9 @@ struct FinArgs {
     int cc_lds, cc_lds_off;      // cc_lds: class counts in thread-private LDS columns ([class][thread] int32), which start
                                  // cc_lds_off doubles x blockDim.x into the block's dynamic LDS; else the global scratch `cc`
     int dosage;                  // 1: no allele-frequency filters here (the caller applies them)
-    int wave_regress;            // 1: the regression is left to k_assoc_regress_wave (wide designs)
+    int wave_regress;            // 1: the regression is left to k_assoc_regress_wave (wide designs) / k_assoc_regress_multi
+    int n_out;                   // outcome rows T at the head of the M scanned rows: the design has 1 + (M - T) columns + genotype
+    double* outcome_f64;         // [L, T, TRK_AO_COLS] of trk_assoc_scan_multi (null: trk_assoc_scan)
 };
 
 // index of Gram entry (r, c), r <= c, rows 0..M (row M = ones), row-major upper triangle
@@ -1881,6 +1895,7 @@ __global__ __launch_bounds__(FIN_T) void k_assoc_finalize(const FinArgs a) {
     if (l >= a.b.n_loci) return;
     const int M = a.M, L = a.b.n_loci;
     const int P = M + 1;  // design columns: ones, covariates 1..M-1, genotype (last)
+    const int ncols = M - a.n_out + 2;  // ones, covariates, genotype: what 'n covars >= n samples' counts (M + 1 with one outcome)
 #define LW(e) fin_lds[(size_t)(e) * blockDim.x + threadIdx.x]
     int32_t* li = a.locus_int + (size_t)l * TRK_AI_COLS;
     double* lf = a.locus_f64 + (size_t)l * TRK_AF_COLS;
@@ -1934,7 +1949,7 @@ __global__ __launch_bounds__(FIN_T) void k_assoc_finalize(const FinArgs a) {
     li[TRK_AI_N_RALLELES] = R;
     int status = TRK_AS_OK;
     if (a.dosage) {
-        if (M + 1 >= n) status = TRK_AS_N_COVARS;
+        if (ncols >= n) status = TRK_AS_N_COVARS;
     } else if (R == 0) {
         status = TRK_AS_NO_CALLED;
     } else if (R == 1) {
@@ -1947,7 +1962,7 @@ __global__ __launch_bounds__(FIN_T) void k_assoc_finalize(const FinArgs a) {
         lf[TRK_AF_NONMAJOR] = nonmajor;
         if (nonmajor < a.cutoff)
             status = TRK_AS_NON_MAJOR;
-        else if (M + 1 >= n)
+        else if (ncols >= n)
             status = TRK_AS_N_COVARS;
     }
     if (status != TRK_AS_OK) {
@@ -2224,6 +2239,171 @@ __global__ __launch_bounds__(WAVE* RW_WAVES) void k_assoc_regress_wave(const Fin
 #undef AT
 }
 
+// -------------------------------------------------------------------------------------------
+// trk_assoc_scan_multi: T outcomes against the same K covariates, ONE factorisation per locus.  The scan ran over
+// M = T + K rows (outcomes first), so a locus's record holds g'y_t, C'y_t and y_t'y_t for every t.  One wave per
+// locus; P = K + 2 design columns [ones, covariates, genotype]:
+//   lane i < P       row i of the normal matrix, packed lower triangle in LDS (as k_assoc_regress_wave<1>);
+//   lane P + t       outcome t's right-hand side as one more row of the tile, L_(P+t) j = z_t j: the left-looking
+//                    Cholesky forward-substitutes all T of them in the step that finishes column j.  These rows are
+//                    stored COLUMN-major ([P][T]: the outcome lanes of a step touch T consecutive doubles).
+// P + T = M + 2 <= 64 rows, one per lane.  Which columns are dropped, the rank and TRK_AS_COLLINEAR depend on the
+// design alone: decided once.  The epilogue (|z_t|^2, ssr, se, t, R^2, Student-t tail) runs on the T outcome lanes side
+// by side; lane P + t stores row t of outcome_f64, lane P also outcome 0's values into locus_f64.  Of the Gram triangle
+// of [vec..., 1] only design x design, outcome x design and the outcomes' diagonal are read.
+// -------------------------------------------------------------------------------------------
+constexpr int RM_WAVES = 4;
+__global__ __launch_bounds__(WAVE* RM_WAVES) void k_assoc_regress_multi(const FinArgs a) {
+    extern __shared__ double rm_lds[];
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x >> 6;
+    const int l = blockIdx.x * RM_WAVES + wid;
+    if (l >= a.b.n_loci) return;
+    const int M = a.M, L = a.b.n_loci, T = a.n_out, K = M - T, P = K + 2;
+    const int t = lane - P;                    // this lane's outcome
+    const bool olane = t >= 0 && t < T;
+    int32_t* li = a.locus_int + (size_t)l * TRK_AI_COLS;
+    double* lf = a.locus_f64 + (size_t)l * TRK_AF_COLS;
+    double* orow = a.outcome_f64 + ((size_t)l * T + (olane ? t : 0)) * TRK_AO_COLS;
+    if (li[TRK_AI_STATUS] != TRK_AS_OK || li[TRK_AI_RANK] != -1) {   // filtered by k_assoc_finalize: nothing is tested
+        if (olane)
+            for (int c = 0; c < TRK_AO_COLS; ++c) orow[c] = NAN;
+        return;
+    }
+    const int ntri = P * (P + 1) / 2;
+    double* A = rm_lds + (size_t)wid * (ntri + P * T);
+#define AT(i, k) A[(i) * ((i) + 1) / 2 + (k)]
+#define RHS(tt, k) A[ntri + (k) * T + (tt)]
+    // this lane's own row, column k: ROW(k)
+    const int rbase = lane < P ? lane * (lane + 1) / 2 : ntri + (olane ? t : 0), rstride = lane < P ? 1 : T;
+#define ROW(k) A[rbase + (k) * rstride]
+    auto psum = [&](int col) {
+        double v = 0.0;
+        for (int ch = 0; ch < a.nchunks; ++ch) v += a.partial[((size_t)ch * L + l) * a.NS + col];
+        return v;
+    };
+    auto G = [&](int r, int c) {   // Gram entry of vector rows r <= c (row M = ones) over the locus's called samples
+        const int e = gidx(r, c, M);
+        return a.full[e] - psum(3 + M + e);
+    };
+    auto dcol = [&](int r) { return r == M ? 0 : r - T + 1; };   // vector row >= T -> design column
+    const double n_d = (double)li[TRK_AI_N_TESTED];
+    const double mean = lf[TRK_AF_COLS - 1], sd = lf[TRK_AF_GT_STD];
+    // ---- build: T (K + 1) outcome x design entries, then the (K + 1)(K + 2) / 2 of the design block, 64 per step ----
+    {
+        const int K1 = K + 1, nrhs = T * K1, need = nrhs + K1 * (K1 + 1) / 2;
+        for (int q = lane; q < need; q += WAVE) {
+            if (q < nrhs) {
+                const int r = q / K1, c = T + (q - r * K1);
+                RHS(r, dcol(c)) = G(r, c);
+            } else {
+                int r = 0, pos = q - nrhs;             // row r of the design block's triangle, column r + pos
+                while (r < K1 && pos >= K1 - r) {
+                    pos -= K1 - r;
+                    ++r;
+                }
+                const int ir = dcol(T + r), ic = dcol(T + r + pos);
+                const double val = G(T + r, T + r + pos);
+                if (ir > ic) AT(ir, ic) = val;
+                else AT(ic, ir) = val;
+            }
+        }
+    }
+    wave_fence();
+    double sy = 0.0, yy = 0.0;
+    if (lane <= K) {               // the genotype's row K + 1: sum g~ * column_j = (sum g * col_j - mean * sum col_j) / sd
+        const double sgc = lane == 0 ? psum(1) : psum(3 + T + lane - 1);
+        const double sc = lane == 0 ? n_d : AT(lane, 0);
+        AT(K + 1, lane) = (sgc - mean * sc) / sd;
+    } else if (lane == K + 1) {
+        AT(K + 1, K + 1) = n_d;    // g~ ' g~
+    } else if (olane) {
+        sy = RHS(t, 0);
+        yy = G(t, t);
+        RHS(t, K + 1) = (psum(3 + t) - mean * sy) / sd;
+    }
+    wave_fence();
+    // ---- left-looking Cholesky; rows j..P+T-1 (the T right-hand sides ride along) are updated for column j --------
+    int rank = 0;
+    bool last_dependent = false;
+    const bool row_live = lane < P + T;
+    for (int j = 0; j < P; ++j) {
+        double v = 0.0;
+        if (row_live && lane >= j) {
+            v = ROW(j);
+            for (int k = 0; k < j; ++k) v -= ROW(k) * AT(j, k);
+        }
+        const double ajj = AT(j, j);  // still the original diagonal entry
+        const double d = __shfl(v, j, WAVE);
+        wave_fence();
+        if (!(d > 1e-11 * ajj)) {  // column in the span of the previous ones: dropped (pinv semantics)
+            if (row_live && lane >= j) ROW(j) = 0.0;
+            if (j == P - 1) last_dependent = true;
+        } else {
+            const double ljj = sqrt(d);
+            if (lane == j) ROW(j) = ljj;
+            else if (row_live && lane > j) ROW(j) = v / ljj;
+            ++rank;
+        }
+        wave_fence();
+    }
+    if (!olane) return;
+    if (t == 0) {
+        li[TRK_AI_RANK] = rank;
+        if (last_dependent) li[TRK_AI_STATUS] = TRK_AS_COLLINEAR;
+        lf[TRK_AF_COLS - 1] = NAN;
+    }
+    if (last_dependent) {
+        for (int c = 0; c < TRK_AO_COLS; ++c) orow[c] = NAN;
+        return;
+    }
+    // ---- per outcome, side by side -----------------------------------------------------------
+    double zz = 0.0;
+    for (int j = 0; j < P; ++j) {
+        const double z = ROW(j);
+        zz += z * z;
+    }
+    const double lpp = AT(K + 1, K + 1), zp = ROW(K + 1);
+    const double df = n_d - (double)rank;
+    const double ssr = yy - zz;
+    const double scale = ssr / df;
+    const double coef = zp / lpp;
+    const double se = sqrt(scale) / lpp;
+    const double tval = coef / se;
+    const double tss = yy - sy * sy / n_d;
+    const double rsq = 1.0 - ssr / tss;
+    const double pval = trkmath::student_t_two_sided(tval, df);
+    orow[TRK_AO_PVAL] = pval;
+    orow[TRK_AO_COEF] = coef;
+    orow[TRK_AO_SE] = se;
+    orow[TRK_AO_RSQUARED] = rsq;
+    orow[TRK_AO_TVALUE] = tval;
+    if (t == 0) {
+        lf[TRK_AF_PVAL] = pval;
+        lf[TRK_AF_COEF] = coef;
+        lf[TRK_AF_SE] = se;
+        lf[TRK_AF_RSQUARED] = rsq;
+        lf[TRK_AF_TVALUE] = tval;
+        lf[TRK_AF_DF_RESID] = df;
+    }
+#undef ROW
+#undef RHS
+#undef AT
+}
+
+// n_outcomes == 1 through trk_assoc_scan_multi: the single-outcome kernels did the work; their five columns as [L, 1, 5]
+__global__ __launch_bounds__(256) void k_assoc_outcome_copy(const double* __restrict__ locus_f64, double* __restrict__ outcome_f64,
+                                                            int n_loci) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_loci) return;
+    const double* lf = locus_f64 + (size_t)l * TRK_AF_COLS;
+    double* o = outcome_f64 + (size_t)l * TRK_AO_COLS;
+    o[TRK_AO_PVAL] = lf[TRK_AF_PVAL];
+    o[TRK_AO_COEF] = lf[TRK_AF_COEF];
+    o[TRK_AO_SE] = lf[TRK_AF_SE];
+    o[TRK_AO_RSQUARED] = lf[TRK_AF_RSQUARED];
+    o[TRK_AO_TVALUE] = lf[TRK_AF_TVALUE];
+}
+
 
 // -------------------------------------------------------------------------------------------
 // wide designs (32..126 vector rows; 63 and more always, 32..62 outside the one-pass MFMA kernel's conditions): the
@@ -2420,8 +2600,20 @@ static hipError_t launch_regress_wave(const FinArgs& f, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// T outcomes of one locus per wave: the tile is the design's packed triangle + T right-hand sides (at most 2079 doubles)
+static hipError_t launch_regress_multi(const FinArgs& f, hipStream_t stream) {
+    const int T = f.n_out, P = f.M - T + 2;
+    if (T < 2 || P < 2 || P + T > WAVE || !f.outcome_f64) return hipErrorInvalidValue;
+    const size_t lds = (size_t)RM_WAVES * (P * (P + 1) / 2 + P * T) * 8;
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assoc_regress_multi),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_assoc_regress_multi, dim3((f.b.n_loci + RM_WAVES - 1) / RM_WAVES), dim3(WAVE * RM_WAVES), lds, stream, f);
+    return hipGetLastError();
+}
+
 static void assoc_build(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out, void* workspace,
-                        AssocPlan& p, AssocArgs& a, FinArgs& f, double*& full) {
+                        AssocPlan& p, AssocArgs& a, FinArgs& f, double*& full, int n_out = 1) {
     const int M = prm.n_vec;
     p = assoc_plan(b, M);
     a = AssocArgs{};
@@ -2437,6 +2629,7 @@ static void assoc_build(const trk_batch& b, const trk_assoc_params& prm, const t
     a.loci_per_wg = p.loci_per_wg;
     a.wave_bytes = p.wave_bytes;
     a.kshift = p.kshift;
+    a.n_out = n_out;
     int e = 0;
     for (int r = 0; r <= M && M <= AS_MAXV; ++r)
         for (int c = r; c <= M; ++c) {
@@ -2476,6 +2669,8 @@ static void assoc_build(const trk_batch& b, const trk_assoc_params& prm, const t
     f.NC = a.NC;
     f.nchunks = p.nchunks;
     f.wave_regress = (use_wave_regress(M) || M > AS_MAXV) ? 1 : 0;   // wide designs: always a wave per locus
+    f.n_out = n_out;
+    if (n_out > 1) f.wave_regress = 1;   // T outcomes: k_assoc_regress_multi, whatever the width
 }
 
 // step 1 (cheap): zero the scratch, Gram matrix of the regression set
@@ -2572,12 +2767,12 @@ static hipError_t launch_assoc_scan_wide(const trk_batch& b, const trk_assoc_par
 
 // step 2: the streaming pass over the genotype tensor
 hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
-                             void* workspace, int n_cu, hipStream_t stream) {
+                             void* workspace, int n_cu, hipStream_t stream, int n_outcomes) {
     AssocPlan p;
     AssocArgs a;
     FinArgs f;
     double* full;
-    assoc_build(b, prm, out, workspace, p, a, f, full);
+    assoc_build(b, prm, out, workspace, p, a, f, full, n_outcomes);
     // wide designs (32-62 trait columns): three or four 16-row tiles in ONE pass of the MFMA kernel; batches outside
     // the streaming conditions (and TRK_AS_WIDE_PAIRS=1) go pair of row groups by pair of row groups
     if (prm.n_vec > AS_MAXV && !(p.fast && p.mfma_rt))
@@ -2609,6 +2804,24 @@ hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, co
         // the Gram correction of every locus's missing calls, from the bits the scan left
         const size_t gm_lds = (size_t)GM_WAVES * GM_LIST * 4;
         const unsigned gm_grid = (unsigned)((b.n_loci + GM_WAVES - 1) / GM_WAVES);
+        if (n_outcomes > 1) {
+            // the multi-outcome form: no outcome x outcome products (TO = whole 16-row tiles of outcomes where that
+            // frees a tile pair: the last tile holds the ones row, one outcome tile alone pairs with nothing skippable)
+            int to = n_outcomes / 16;
+            if (to > p.mfma_rt - 1) to = p.mfma_rt - 1;
+            if (to < 2) to = 0;
+#define TRK_GM_LAUNCH(RT_, TO_) \
+    hipLaunchKernelGGL((k_assoc_gram_miss<RT_, TO_>), dim3(gm_grid), dim3(WAVE * GM_WAVES), gm_lds, stream, a)
+            if (p.mfma_rt == 1) TRK_GM_LAUNCH(1, 0);
+            else if (p.mfma_rt == 2) TRK_GM_LAUNCH(2, 0);
+            else if (p.mfma_rt == 3 && to == 0) TRK_GM_LAUNCH(3, 0);
+            else if (p.mfma_rt == 3) TRK_GM_LAUNCH(3, 2);
+            else if (to == 0) TRK_GM_LAUNCH(4, 0);
+            else if (to == 2) TRK_GM_LAUNCH(4, 2);
+            else TRK_GM_LAUNCH(4, 3);
+#undef TRK_GM_LAUNCH
+            return hipGetLastError();
+        }
         if (p.mfma_rt == 1) hipLaunchKernelGGL(k_assoc_gram_miss<1>, dim3(gm_grid), dim3(WAVE * GM_WAVES), gm_lds, stream, a);
         else if (p.mfma_rt == 2) hipLaunchKernelGGL(k_assoc_gram_miss<2>, dim3(gm_grid), dim3(WAVE * GM_WAVES), gm_lds, stream, a);
         else if (p.mfma_rt == 3) hipLaunchKernelGGL(k_assoc_gram_miss<3>, dim3(gm_grid), dim3(WAVE * GM_WAVES), gm_lds, stream, a);
@@ -2630,12 +2843,13 @@ hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, co
 
 // step 3: filters + regression per locus
 hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
-                                 void* workspace, hipStream_t stream) {
+                                 void* workspace, hipStream_t stream, int n_outcomes, double* outcome_f64) {
     AssocPlan p;
     AssocArgs a;
     FinArgs f;
     double* full;
-    assoc_build(b, prm, out, workspace, p, a, f, full);
+    assoc_build(b, prm, out, workspace, p, a, f, full, n_outcomes);
+    f.outcome_f64 = outcome_f64;
     if (b.n_loci == 0) return hipSuccess;
     const int P = prm.n_vec + 1;
     int fin_t = FIN_T;
@@ -2652,7 +2866,14 @@ hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_assoc_finalize, dim3((b.n_loci + fin_t - 1) / fin_t), dim3(fin_t), fin_lds, stream, f);
     if ((err = hipGetLastError()) != hipSuccess) return err;
-    return f.wave_regress ? launch_regress_wave(f, stream) : hipSuccess;
+    if (n_outcomes > 1) return launch_regress_multi(f, stream);
+    if (f.wave_regress && (err = launch_regress_wave(f, stream)) != hipSuccess) return err;
+    if (outcome_f64) {   // trk_assoc_scan_multi with one outcome
+        hipLaunchKernelGGL(k_assoc_outcome_copy, dim3((b.n_loci + 255) / 256), dim3(256), 0, stream, out.locus_f64, outcome_f64,
+                           b.n_loci);
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 // one pass of the dosage kernels over the batch for the design `prm` (at most AS_MAXV rows): records into `workspace`

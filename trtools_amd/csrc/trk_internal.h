@@ -87,10 +87,12 @@ hipError_t launch_binomtest_batch(const int64_t* k, const int64_t* n, const doub
 size_t assoc_workspace_bytes(const trk_batch& b, int n_vec);
 hipError_t launch_assoc_prepare(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
                                 void* workspace, hipStream_t stream);
+// n_outcomes: the first rows of prm.vec that are outcomes (trk_assoc_scan_multi; the others are their shared covariates);
+// outcome_f64: [L, n_outcomes, TRK_AO_COLS] or null
 hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
-                             void* workspace, int n_cu, hipStream_t stream);
+                             void* workspace, int n_cu, hipStream_t stream, int n_outcomes = 1);
 hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
-                                 void* workspace, hipStream_t stream);
+                                 void* workspace, hipStream_t stream, int n_outcomes = 1, double* outcome_f64 = nullptr);
 hipError_t launch_assoc_dosage(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_dosage& dos,
                                const trk_assoc_out& out, double* class_sums, double* locus_sums, void* workspace,
                                hipStream_t stream);

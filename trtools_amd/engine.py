@@ -845,6 +845,34 @@ class Engine:
         self._chk(self.lib.trk_assoc_scan(self.ctx, C.byref(batch.struct), C.byref(prm), C.byref(out.struct)))
         return out
 
+    def assoc_scan_multi(self, batch, vec, n_outcomes, allele_len, rlen_class, sample_in=None, non_major_cutoff=20.0):
+        """trk_assoc_scan_multi: vec [T + K, S] float64, rows 0..T-1 the standardised outcomes, rows T.. the covariates
+        they share (T = n_outcomes, T + K <= ASSOC_MAX_MULTI); the other arguments as assoc_scan.  One pass over the
+        genotype tensor, one factorisation per locus.  Returns (AssocResult -- the per-locus columns, outcome 0 in the
+        regression columns --, outcome_f64 [L, T, AO_COLS] device array: p, coef, se, R^2, t; nan where not tested)."""
+        def dev(x, dt):
+            return x if isinstance(x, DeviceArray) else self.upload(x, dt)
+        vec_d = dev(vec, np.float64)
+        if len(vec_d.shape) != 2 or vec_d.shape[1] != batch.n_samples:
+            raise ValueError("vec must be [T + K, S]")
+        if not 1 <= int(n_outcomes) <= vec_d.shape[0]:
+            raise ValueError("n_outcomes %r outside [1, %d rows of vec]" % (n_outcomes, vec_d.shape[0]))
+        len_d, rc_d = dev(allele_len, np.float64), dev(rlen_class, np.uint16)
+        in_d = dev(sample_in, np.uint8) if sample_in is not None else None
+        out = AssocResult(self.empty((batch.n_loci, L.AI_COLS), np.int32),
+                          self.empty((batch.n_loci, L.AF_COLS), np.float64),
+                          self.empty((batch.sum_alleles,), np.int32))
+        per_outcome = self.empty((batch.n_loci, int(n_outcomes), L.AO_COLS), np.float64)
+        prm = L.AssocParams()
+        prm.n_vec, prm.flags = vec_d.shape[0], 0
+        prm.vec, prm.allele_len, prm.rlen_class = vec_d.ptr, len_d.ptr, rc_d.ptr
+        prm.sample_in = in_d.ptr if in_d is not None else None
+        prm.non_major_cutoff = float(non_major_cutoff)
+        out._keep = (vec_d, len_d, rc_d, in_d)
+        self._chk(self.lib.trk_assoc_scan_multi(self.ctx, C.byref(batch.struct), C.byref(prm), int(n_outcomes),
+                                                C.byref(out.struct), per_outcome.ptr))
+        return out, per_outcome
+
     def assoc_scan_dosage(self, batch, vec, allele_len, rlen_class, ap1, ap2, perm, dclass, dclass_value, best_class,
                           sample_in=None):
         """trk_assoc_scan_dosage.  ap1/ap2 [L, S, K] float32; perm int32 / dclass uint16 / dclass_value float64 /
