@@ -480,6 +480,7 @@ enum {
     TRK_AI_RANK = 3,       /* rank of the design (df_resid = n - rank)                       */
     TRK_AI_N_BAD = 4,      /* calls with an allele index >= A_l                               */
     TRK_AI_N_HAPS = 5,     /* called haplotypes among curr_samples (denominator of the AFs)  */
+    TRK_AI_N_ITER = 6,     /* trk_assoc_scan_logistic: Newton steps taken (0 elsewhere)      */
     TRK_AI_COLS = 8
 };
 enum {
@@ -489,7 +490,9 @@ enum {
     TRK_AS_NON_MAJOR = 3,      /* 'non-major allele count<cutoff'                            */
     TRK_AS_N_COVARS = 4,       /* 'n covars >= n samples'                                    */
     TRK_AS_ZERO_VARIANCE = 5,  /* summed genotype constant over curr_samples (reference: 0/0) */
-    TRK_AS_COLLINEAR = 6       /* genotype in the span of the covariates                     */
+    TRK_AS_COLLINEAR = 6,      /* genotype in the span of the covariates                     */
+    TRK_AS_CONSTANT_OUTCOME = 7, /* trk_assoc_scan_logistic: the outcome is all 0 or all 1 over curr_samples */
+    TRK_AS_NOT_CONVERGED = 8   /* trk_assoc_scan_logistic: no maximum found (separation among the causes) */
 };
 /* trk_assoc_out.locus_f64 columns ([L, TRK_AF_COLS] float64); nan where not tested */
 enum {
@@ -502,6 +505,7 @@ enum {
     TRK_AF_TVALUE = 6,
     TRK_AF_DF_RESID = 7,
     TRK_AF_NONMAJOR = 8,  /* np.sum(af)*n_samples*2 of load_and_filter_genotypes.py:236     */
+    TRK_AF_LOGLIK = 9,    /* trk_assoc_scan_logistic: log-likelihood at the fit (nan elsewhere) */
     TRK_AF_COLS = 10
 };
 typedef struct {
@@ -533,6 +537,26 @@ enum {
 };
 int trk_assoc_scan_multi(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, int32_t n_outcomes,
                          trk_assoc_out* out, double* outcome_f64);
+
+/* Logistic regression of a 0/1 outcome (the reference's unfinished `--binary logistic`, associaTR.py:292-302): for
+ * every locus that trk_assoc_scan leaves at TRK_AS_OK -- same tested samples, counts, histogram, filters, GT_MEAN and
+ * GT_STD, computed by the same scan and finaliser -- the maximum-likelihood fit of
+ *     LL(b) = sum_s y_s eta_s - log(1 + exp(eta_s)),   eta = X b,   X = [1, c_1..c_K, g]
+ * over curr_samples, with y = vec[0] the RAW 0/1 outcome, c_k = vec[k] the caller's standardised covariates and g the
+ * summed length standardised over curr_samples (GT_MEAN, GT_STD).  n_vec = 1 + K, K <= TRK_ASSOC_MAX_LOGIT_COVARS (the
+ * design is one 16-row matrix tile; more is TRK_ERR_ARG).  Any ploidy, any row alignment.
+ *   Newton steps b += H^-1 grad, H = X' W X, W = diag(mu (1 - mu)), grad = X' (y - mu), from b = 0 except the
+ *   intercept = logit(mean y); converged when after a step max_j |delta_j| <= 1e-9 max(1, max_j |b_j|); at most 30 steps.
+ *   Rank: decided in the first factorisation (W = const I there) by the linear finaliser's rule d > 1e-11 a_jj; a
+ *   covariate dropped there stays out; a dependent genotype column is TRK_AS_COLLINEAR.
+ *   COEF = b_g, SE = sqrt((H^-1)_gg) at the final b, TVALUE = z = COEF / SE, PVAL = erfc(|z| / sqrt 2),
+ *   DF_RESID = n - rank, RSQUARED = nan, LOGLIK = LL at the fit, TRK_AI_N_ITER = steps taken.
+ *   TRK_AS_CONSTANT_OUTCOME: y all 0 or all 1 over curr_samples.  TRK_AS_NOT_CONVERGED: 30 steps without convergence, a
+ *   non-finite b, or a kept column failing the pivot rule in a later step (separation ends by one of these).  The
+ *   regression columns and LOGLIK are nan for both; GT_MEAN / GT_STD / NONMAJOR stay as the scan wrote them.
+ * No float atomics: a rerun gives the same bits. */
+#define TRK_ASSOC_MAX_LOGIT_COVARS 13
+int trk_assoc_scan_logistic(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out);
 
 /* associaTR --beagle-dosages (load_and_filter_genotypes.py:179-215, associaTR.py:266-273): the
  * regressor is the expected summed length from the Beagle AP1/AP2 allele probabilities,

@@ -217,6 +217,10 @@ AI_N_TESTED, AI_STATUS, AI_N_RALLELES, AI_RANK, AI_N_BAD, AI_N_HAPS, AI_COLS = 0
 (AF_PVAL, AF_COEF, AF_SE, AF_RSQUARED, AF_GT_STD, AF_GT_MEAN, AF_TVALUE, AF_DF_RESID, AF_NONMAJOR) = range(9)
 AF_COLS = 10
 (AS_OK, AS_NO_CALLED, AS_ONE_ALLELE, AS_NON_MAJOR, AS_N_COVARS, AS_ZERO_VARIANCE, AS_COLLINEAR) = range(7)
+# trk_assoc_scan_logistic: covariates of one 16-row design tile, its two columns and two statuses
+ASSOC_MAX_LOGIT_COVARS = 13
+AI_N_ITER, AF_LOGLIK = 6, 9
+AS_CONSTANT_OUTCOME, AS_NOT_CONVERGED = 7, 8
 # trk_assoc_scan_multi: outcomes + covariates (TRK_ASSOC_MAX_MULTI), columns of outcome_f64 [L, T, AO_COLS]
 ASSOC_MAX_MULTI = 62
 AO_PVAL, AO_COEF, AO_SE, AO_RSQUARED, AO_TVALUE, AO_COLS = 0, 1, 2, 3, 4, 5
@@ -247,7 +251,7 @@ EXPORTS = [
     'trk_locus_stats', 'trk_locus_finalize', 'trk_call_filters', 'trk_locus_filters',
     'trk_comm_unique_id', 'trk_comm_init', 'trk_allreduce_sum_i64', 'trk_allgather',
     'trk_binomtest_two_sided', 'trk_binom_pmf', 'trk_binomtest_batch', 'trk_synth_fill', 'trk_synth_fill_gangstr', 'trk_test_set_option', 'trk_test_get_option',
-    'trk_assoc_scan', 'trk_assoc_scan_multi', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_mosaic_fit', 'trk_parse_reads', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
+    'trk_assoc_scan', 'trk_assoc_scan_multi', 'trk_assoc_scan_logistic', 'trk_assoc_scan_dosage', 'trk_student_t_two_sided', 'trk_dosages', 'trk_qc_reduce', 'trk_compare', 'trk_mosaic_fit', 'trk_parse_reads', 'trk_parse_samples', 'trk_format_samples', 'trk_inflate_blocks', 'trk_inflate_hook', 'trk_inflate_hook_async', 'trk_inflate_text', 'trk_inflate_stats', 'trk_deflate_bgzf', 'trk_deflate_bound', 'trk_planarize', 'trk_pad_rows', 'trk_permute_columns', 'trk_stream_probe', 'trk_device_clocks', 'trk_stream_select', 'trk_stream_wait',
     'trk_host_alloc', 'trk_host_free', 'trk_memcpy_h2d_async', 'trk_memcpy_d2h_async', 'trk_queue_sync', 'trk_thread_queue', 'trk_exchange', 'trk_event_record', 'trk_event_wait',
 ]
 
@@ -259,7 +263,7 @@ class TrkError(RuntimeError):
 
 
 # the sources libtrk.so is built from, in the order csrc/Makefile hashes them
-_SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_binom.h', 'csrc/trk_compare.hip', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
+_SOURCES = ['csrc/trk_api.hip', 'csrc/trk_assoc.hip', 'csrc/trk_assoc_logit.hip', 'csrc/trk_binom.h', 'csrc/trk_compare.hip', 'csrc/trk_deflate.hip', 'csrc/trk_hwe.hip', 'csrc/trk_inflate.hip', 'csrc/trk_internal.h', 'csrc/trk_kernels.hip',
             'csrc/trk_mosaic.hip', 'csrc/trk_parse.hip', 'csrc/trk_qc.hip', 'csrc/trk_reads.hip', 'csrc/trk_student.h', 'csrc/trk_vcf.cpp', '../include/trk.h', '../include/trk_test.h', '../include/trk_vcf.h']
 
 
@@ -401,6 +405,7 @@ def load():
     lib.trk_binom_pmf.argtypes = [i64, i64, dbl]
     lib.trk_binom_pmf.restype = dbl
     lib.trk_assoc_scan.argtypes = [vp, P(Batch), P(AssocParams), P(AssocOut)]
+    lib.trk_assoc_scan_logistic.argtypes = [vp, P(Batch), P(AssocParams), P(AssocOut)]
     lib.trk_assoc_scan_multi.argtypes = [vp, P(Batch), P(AssocParams), C.c_int32, P(AssocOut), vp]
     lib.trk_assoc_scan_dosage.argtypes = [vp, P(Batch), P(AssocParams), P(AssocDosage), P(AssocOut), vp, vp]
     lib.trk_planarize.argtypes = [vp, vp, vp, i64, C.c_int32]

@@ -9,7 +9,8 @@ tensor, a Cholesky solve and a Student-t tail per locus).
 Host Python assembles the covariates (associaTR.py:138-204), parses / harmonises records and
 formats text; ``--beagle-dosages`` regresses on the expected length from the AP1/AP2 fields
 (``trk_assoc_scan_dosage``).  Not provided (refused loudly): the reference's hidden, unfinished
-``--plotting-phenotype`` family of options.
+``--plotting-phenotype`` family of options.  ``--binary logistic`` (which the reference left commented out) fits a
+0/1 phenotype by maximum likelihood on the device (``trk_assoc_scan_logistic``).
 """
 import argparse
 import datetime
@@ -31,7 +32,9 @@ pval_precision = 2
 BATCH_CELLS = 1 << 24     # loci x samples per device batch
 
 _REASONS = {L.AS_NO_CALLED: 'No called samples', L.AS_ONE_ALLELE: 'Only one called allele',
-            L.AS_N_COVARS: 'n covars >= n samples'}
+            L.AS_N_COVARS: 'n covars >= n samples',
+            L.AS_CONSTANT_OUTCOME: 'outcome constant among called samples',
+            L.AS_NOT_CONVERGED: 'logistic regression did not converge'}
 
 
 def _merge_arrays(a, b):
@@ -64,12 +67,14 @@ def _weighted_binom_conf(weights, successes, confidence):
     return (phat, center - half, center + half)
 
 
-def _load_design(all_samples, trait_fnames, same_samples, sample_fname, n_outcomes=1):
+def _load_design(all_samples, trait_fnames, same_samples, sample_fname, n_outcomes=1, binary=None):
     """Covariate assembly of perform_gwas_helper (associaTR.py:138-204), messages included.
     Returns (sample_filter bool[S], covars [Sf, 1+T] with column 0 reserved for the genotype and
     column 1 the intercept, outcome [Sf], pheno_std).  ``n_outcomes`` > 1 (--n-outcomes): the first n_outcomes trait
     columns are outcomes -- outcome [Sf, n_outcomes], pheno_std [n_outcomes], each outcome standardised by itself --
-    and covars holds the intercept and the remaining columns, as a single-outcome run with these covariates has it."""
+    and covars holds the intercept and the remaining columns, as a single-outcome run with these covariates has it.
+    ``binary`` ('logistic'): the outcome must be 0 / 1 and is returned as it is (pheno_std 1: the coefficient is the
+    log-odds per repeat unit); the covariates are standardised as ever."""
     print('{} samples in the VCF'.format(len(all_samples)), flush=True)
     if not same_samples:
         covars = np.load(trait_fnames[0])
@@ -126,8 +131,13 @@ def _load_design(all_samples, trait_fnames, same_samples, sample_fname, n_outcom
         covars[:, 1] = 1
         return sample_filter, covars, outcome, pheno_std
     pheno_std = np.std(covars[:, 1])
+    raw_outcome = covars[:, 1].copy()
+    if binary and not np.all((raw_outcome == 0) | (raw_outcome == 1)):
+        raise ValueError("associaTR: --binary %s needs a phenotype of 0 / 1 values" % binary)
     covars = (covars - np.mean(covars, axis=0)) / np.std(covars, axis=0)
     outcome = covars[:, 1].copy()
+    if binary:
+        outcome, pheno_std = raw_outcome, 1.0
     covars[:, 1] = 1
     return sample_filter, covars, outcome, pheno_std
 
@@ -357,7 +367,7 @@ def _write_outcome_rows(out, recs, allele_off, allele_lens, res, per, pheno_std,
                     non_major_cutoff)
 
 
-def _flush(records, outfile, vec, sample_filter, pheno_std, non_major_cutoff, beagle_dosages=False):
+def _flush(records, outfile, vec, sample_filter, pheno_std, non_major_cutoff, beagle_dosages=False, binary=None):
     """One device batch of record objects -> output rows."""
     if not records:
         return
@@ -376,8 +386,9 @@ def _flush(records, outfile, vec, sample_filter, pheno_std, non_major_cutoff, be
         _write_rows(outfile, records, hb.allele_off, hb.allele_lens, res, pheno_std, non_major_cutoff,
                     dosage=(class_sums, locus_sums))
     else:
-        res = runtime.get_compute().assoc_batch(hb, vec, sample_filter, non_major_cutoff,
-                                                precision=lf_mod.allele_len_precision)
+        compute = runtime.get_compute()
+        scan = compute.assoc_logistic_batch if binary else compute.assoc_batch
+        res = scan(hb, vec, sample_filter, non_major_cutoff, precision=lf_mod.allele_len_precision)
         _write_rows(outfile, records, hb.allele_off, hb.allele_lens, res, pheno_std, non_major_cutoff)
 
 
@@ -396,7 +407,7 @@ def _batch_path_ok(reader, vcftype, region, beagle_dosages, period_check):
             len(reader.samples) > 0 and _knobs.lab('TRK_ASSOC_BATCH', '1') != '0')
 
 
-def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, non_major_cutoff, batch_loci):
+def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, non_major_cutoff, batch_loci, binary=None):
     """perform_gwas_helper's loop (associaTR.py:246-293) a batch of records at a time.  Returns the number of loci."""
     from .. import _knobs
     from ..batch import HostBatch
@@ -443,7 +454,7 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
                     if keep is None or keep[l]]
             n_loci += len(recs)
             if shard.next_batch():
-                _flush(recs, shard, vec, sample_filter, pheno_std, non_major_cutoff)
+                _flush(recs, shard, vec, sample_filter, pheno_std, non_major_cutoff, binary=binary)
                 shard.end_batch()
             continue
         n_loci += rb.n
@@ -458,6 +469,9 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
         if isinstance(shard, _MultiOut):
             res, per = compute.assoc_multi_batch(hb, vec, len(shard.outs), sample_filter, non_major_cutoff,
                                                  precision=lf_mod.allele_len_precision, tables=tables)
+        elif binary:
+            res = compute.assoc_logistic_batch(hb, vec, sample_filter, non_major_cutoff,
+                                               precision=lf_mod.allele_len_precision, tables=tables)
         elif getattr(compute, 'eng', None) is not None:
             res = compute.assoc_batch(hb, vec, sample_filter, non_major_cutoff, precision=lf_mod.allele_len_precision,
                                       tables=tables)
@@ -482,7 +496,7 @@ def _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, 
 
 
 def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait_fnames, same_samples, sample_fname,
-                        non_major_cutoff, beagle_dosages=False, attach=None, n_outcomes=1):
+                        non_major_cutoff, beagle_dosages=False, attach=None, n_outcomes=1, binary=None):
     """Header, covariates, batched scan (associaTR.py:117-372 without the plotting statistics).  ``n_outcomes`` > 1:
     ``outfile`` is a list of n_outcomes open files and ``phenotype_name`` their comma-separated names, one table each."""
     from .. import dist
@@ -494,8 +508,11 @@ def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait
             f.write('se_{}\tregression_R^2\t'.format(name))
             f.flush()
     sample_filter, covars, outcome, pheno_std = _load_design(all_samples, trait_fnames, same_samples, sample_fname,
-                                                             n_outcomes)
+                                                             n_outcomes, binary)
     vec = _device_vectors(sample_filter, covars, outcome, beagle_dosages)
+    if binary and vec.shape[0] - 1 > L.ASSOC_MAX_LOGIT_COVARS:
+        raise ValueError("associaTR: --binary %s with %d covariates; this build fits at most %d"
+                         % (binary, vec.shape[0] - 1, L.ASSOC_MAX_LOGIT_COVARS))
     if rank == 0:
         fields = list(load_and_filter_genotypes.DETAIL_FIELDS)
         if beagle_dosages:
@@ -515,7 +532,7 @@ def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait
 
     def emit(recs):
         if recs and shard.next_batch():
-            _flush(recs, shard, vec, sample_filter, pheno_std, non_major_cutoff, beagle_dosages)
+            _flush(recs, shard, vec, sample_filter, pheno_std, non_major_cutoff, beagle_dosages, binary)
             shard.end_batch()
 
     batch = attach.get('batch') if attach is not None else None
@@ -524,7 +541,8 @@ def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait
     if batch:
         reader, vcftype, region = batch
         shard.attach(reader, region)
-        n_loci = _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, non_major_cutoff, batch_loci)
+        n_loci = _run_batches(reader, vcftype, region, shard, vec, sample_filter, pheno_std, non_major_cutoff, batch_loci,
+                              binary)
     else:
         for trrecord in record_iter:
             records.append(trrecord)
@@ -544,13 +562,21 @@ def perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, trait
 
 def perform_gwas(outfname, tr_vcf, phenotype_name, traits_fnames, vcftype, same_samples, sample_fname, region,
                  non_major_cutoff, beagle_dosages, plotting_phenotype_fname, paired_genotype_plot,
-                 plot_phenotype_residuals, plotting_ci_alphas, imputed_ukb_strs_paper_period_check, n_outcomes=1):
+                 plot_phenotype_residuals, plotting_ci_alphas, imputed_ukb_strs_paper_period_check, n_outcomes=1, binary=None):
     """Signature of the reference (associaTR.py:432-482), plus ``n_outcomes`` (--n-outcomes T): the first T trait
     columns are outcomes regressed on the same covariates in one pass over the genotypes, ``phenotype_name`` their T
-    comma-separated names, and table t is written to ``<outfname>.<name t>``."""
+    comma-separated names, and table t is written to ``<outfname>.<name t>``; and ``binary`` (--binary logistic, the
+    spelling the reference left commented out): logistic regression of a 0 / 1 phenotype (trk_assoc_scan_logistic),
+    p / coeff / se columns as ever, coeff the log-odds per repeat unit, regression_R^2 nan."""
     if plotting_phenotype_fname or paired_genotype_plot or plot_phenotype_residuals or plotting_ci_alphas:
         raise NotImplementedError("the hidden --plotting-phenotype options of the reference are not provided")
     n_outcomes = int(n_outcomes)
+    if binary not in (None, 'logistic'):
+        raise ValueError("--binary %r: only 'logistic' is provided" % (binary,))
+    if binary and beagle_dosages:
+        raise ValueError("--binary logistic with --beagle-dosages: the logistic fit regresses on the called genotypes only")
+    if binary and n_outcomes > 1:
+        raise ValueError("--binary logistic with --n-outcomes %d: the logistic fit takes one outcome per run" % n_outcomes)
     names = phenotype_name.split(',')
     if n_outcomes < 1:
         raise ValueError("--n-outcomes must be at least 1")
@@ -596,7 +622,7 @@ def perform_gwas(outfname, tr_vcf, phenotype_name, traits_fnames, vcftype, same_
     print("Writing output to {}.temp".format(outfname), flush=True)
     with open(temp, 'w') as outfile:
         perform_gwas_helper(outfile, all_samples, record_iter, phenotype_name, traits_fnames, same_samples,
-                            sample_fname, non_major_cutoff, beagle_dosages, attach=attach)
+                            sample_fname, non_major_cutoff, beagle_dosages, attach=attach, binary=binary)
     if rank != 0:
         import os
         os.remove(temp)               # only rank 0's file holds the merged table
@@ -637,6 +663,11 @@ def getargs():  # pragma: no cover
                              "phenotype_name is then N comma-separated names and table i is written to "
                              "<outfile>.<name i>; each is the table a run on that outcome alone writes. Outcomes + "
                              "covariates: at most 62. Not with --beagle-dosages.")
+    parser.add_argument('--binary', choices=['logistic'], default=None,
+                        help="The phenotype is a 0/1 trait: fit a logistic regression per locus (maximum likelihood by "
+                             "Newton steps on the GPU) instead of the linear one. The phenotype is not standardised; "
+                             "coeff and se are log-odds per repeat unit, regression_R^2 is nan. At most 13 covariates. "
+                             "Not with --beagle-dosages or --n-outcomes.")
     parser.add_argument('--plotting-phenotype', help=argparse.SUPPRESS)
     parser.add_argument('--paired-genotype-plot', action='store_true', default=False, help=argparse.SUPPRESS)
     parser.add_argument('--plot-phenotype-residuals', action='store_true', default=False, help=argparse.SUPPRESS)
@@ -655,7 +686,8 @@ def main(args):
     perform_gwas(args.outfile, args.tr_vcf, args.phenotype_name, args.traits, args.vcftype, args.same_samples,
                  args.sample_list, args.region, args.non_major_cutoff, args.beagle_dosages, args.plotting_phenotype,
                  args.paired_genotype_plot, args.plot_phenotype_residuals, args.plotting_ci_alphas,
-                 args.imputed_ukb_strs_paper_period_check, n_outcomes=getattr(args, 'n_outcomes', 1))
+                 args.imputed_ukb_strs_paper_period_check, n_outcomes=getattr(args, 'n_outcomes', 1),
+                 binary=getattr(args, 'binary', None))
 
 
 def run():  # pragma: no cover

@@ -202,6 +202,17 @@ class DeviceCompute:
         self._free(b, alen_d, rcls_d, sin_d, res.locus_int, res.locus_f64, res.allele_count)
         return out
 
+    def assoc_logistic_batch(self, hb, vec, sample_in, non_major_cutoff, precision=2, tables=None):
+        """associaTR --binary logistic scan of one batch (trk_assoc_scan_logistic): vec [1 + K, S], row 0 the raw 0/1
+        outcome, rows 1.. the standardised covariates; padding and tables as assoc_batch.  Returns AssocHost."""
+        self.eng.check_binary_outcome(vec, sample_in)
+        b, vec_d, sin_d, alen_d, rcls_d = self._assoc_inputs(hb, vec, sample_in, precision, tables)
+        res = self.eng.assoc_scan_logistic(b, vec_d, alen_d, rcls_d, sample_in=sin_d, non_major_cutoff=non_major_cutoff,
+                                           outcome_checked=True)
+        out = AssocHost(res.locus_int.get(), res.locus_f64.get(), res.allele_count.get())
+        self._free(b, alen_d, rcls_d, sin_d, res.locus_int, res.locus_f64, res.allele_count)
+        return out
+
     def assoc_multi_batch(self, hb, vec, n_outcomes, sample_in, non_major_cutoff, precision=2, tables=None):
         """associaTR scan of one batch for ``n_outcomes`` outcomes at once (trk_assoc_scan_multi): vec [T + K, S], rows
         0..T-1 the outcomes, rows T.. their shared covariates; padding and tables as assoc_batch.  Returns (AssocHost,

@@ -813,7 +813,7 @@ int trk_exchange(trk_ctx* ctx, int64_t* sums, size_t n_sums, const void* send, v
 // ---- associaTR scan -----------------------------------------------------------------------
 // trk_assoc_scan (n_outcomes 1, outcome_f64 null) and trk_assoc_scan_multi
 static int assoc_scan_run(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out, int n_outcomes,
-                          double* outcome_f64) {
+                          double* outcome_f64, bool logistic = false) {
     if (!ctx) return TRK_ERR_ARG;
     int rc = check_batch(ctx, in);
     if (rc) return rc;
@@ -826,7 +826,7 @@ static int assoc_scan_run(trk_ctx* ctx, const trk_batch* in, const trk_assoc_par
     if (!out->locus_int || !out->locus_f64 || !out->allele_count)
         return fail(ctx, TRK_ERR_ARG, "assoc outputs are NULL");
     (void)hipSetDevice(ctx->device);
-    const size_t need = trk::assoc_workspace_bytes(*in, prm->n_vec);
+    const size_t need = logistic ? trk::assoc_logit_workspace_bytes(*in, prm->n_vec) : trk::assoc_workspace_bytes(*in, prm->n_vec);
     if (need > ctx->assoc_ws_bytes_[ctx->cur]) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->s()));
         if (ctx->assoc_ws_[ctx->cur]) (void)hipFree(ctx->assoc_ws_[ctx->cur]);
@@ -843,9 +843,20 @@ static int assoc_scan_run(trk_ctx* ctx, const trk_batch* in, const trk_assoc_par
     }
     {
         ProfScope ps(ctx, TRK_K_ASSOC_FINALIZE);
-        HIPCHK(ctx, trk::launch_assoc_finalize(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->s(), n_outcomes, outcome_f64));
+        if (logistic)
+            HIPCHK(ctx, trk::launch_assoc_finalize_logit(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->n_cu, ctx->s()));
+        else
+            HIPCHK(ctx, trk::launch_assoc_finalize(*in, *prm, *out, ctx->assoc_ws_[ctx->cur], ctx->s(), n_outcomes, outcome_f64));
     }
     return TRK_OK;
+}
+
+int trk_assoc_scan_logistic(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out) {
+    if (!ctx) return TRK_ERR_ARG;
+    if (prm && prm->n_vec > 1 + TRK_ASSOC_MAX_LOGIT_COVARS)
+        return fail(ctx, TRK_ERR_ARG, "%d covariates: trk_assoc_scan_logistic takes at most %d (the design is one 16-row matrix tile)",
+                    (int)prm->n_vec - 1, TRK_ASSOC_MAX_LOGIT_COVARS);
+    return assoc_scan_run(ctx, in, prm, out, 1, nullptr, true);
 }
 
 int trk_assoc_scan(trk_ctx* ctx, const trk_batch* in, const trk_assoc_params* prm, trk_assoc_out* out) {

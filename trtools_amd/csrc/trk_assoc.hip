@@ -2841,6 +2841,8 @@ hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, co
     return hipGetLastError();
 }
 
+static hipError_t launch_finalize_kernel(const trk_batch& b, FinArgs& f, hipStream_t stream);
+
 // step 3: filters + regression per locus
 hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
                                  void* workspace, hipStream_t stream, int n_outcomes, double* outcome_f64) {
@@ -2851,7 +2853,21 @@ hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm
     assoc_build(b, prm, out, workspace, p, a, f, full, n_outcomes);
     f.outcome_f64 = outcome_f64;
     if (b.n_loci == 0) return hipSuccess;
-    const int P = prm.n_vec + 1;
+    hipError_t err = launch_finalize_kernel(b, f, stream);
+    if (err != hipSuccess) return err;
+    if (n_outcomes > 1) return launch_regress_multi(f, stream);
+    if (f.wave_regress && (err = launch_regress_wave(f, stream)) != hipSuccess) return err;
+    if (outcome_f64) {   // trk_assoc_scan_multi with one outcome
+        hipLaunchKernelGGL(k_assoc_outcome_copy, dim3((b.n_loci + 255) / 256), dim3(256), 0, stream, out.locus_f64, outcome_f64,
+                           b.n_loci);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// k_assoc_finalize for `f`: the block size and the LDS columns the design's width allows
+static hipError_t launch_finalize_kernel(const trk_batch& b, FinArgs& f, hipStream_t stream) {
+    const int P = f.M + 1;
     int fin_t = FIN_T;
     while (fin_t > 8 && !f.wave_regress && (size_t)(P * (P + 1) / 2 + P) * fin_t * 8 > 150 * 1024) fin_t >>= 1;
     size_t fin_lds = f.wave_regress ? 0 : (size_t)(P * (P + 1) / 2 + P) * fin_t * 8;   // the normal matrix lives in k_assoc_regress_wave
@@ -2865,15 +2881,33 @@ hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds);
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_assoc_finalize, dim3((b.n_loci + fin_t - 1) / fin_t), dim3(fin_t), fin_lds, stream, f);
+    return hipGetLastError();
+}
+
+// trk_assoc_scan_logistic, after the scan: the finaliser stops where it would hand a locus to k_assoc_regress_wave
+// (filters, counts, mean and std written, rank -1 = "regression pending"), k_assoc_vect lays [y, c_1..c_K, 1, 0..] out
+// sample-major behind the scan's workspace, and the Newton kernel takes the pending loci
+size_t assoc_logit_workspace_bytes(const trk_batch& b, int M) {
+    const size_t nsteps = ((size_t)b.n_samples + MF_SB - 1) / MF_SB;
+    return ((assoc_workspace_bytes(b, M) + 255) & ~(size_t)255) + nsteps * MF_SB * 16 * 8;
+}
+
+hipError_t launch_assoc_finalize_logit(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
+                                       void* workspace, int n_cu, hipStream_t stream) {
+    AssocPlan p;
+    AssocArgs a;
+    FinArgs f;
+    double* full;
+    assoc_build(b, prm, out, workspace, p, a, f, full);
+    if (b.n_loci == 0) return hipSuccess;
+    f.wave_regress = 1;
+    hipError_t err = launch_finalize_kernel(b, f, stream);
+    if (err != hipSuccess) return err;
+    a.nsteps = (b.n_samples + MF_SB - 1) / MF_SB;
+    a.vect = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + ((assoc_workspace_bytes(b, prm.n_vec) + 255) & ~(size_t)255));
+    hipLaunchKernelGGL(k_assoc_vect, dim3((n_cu > 0 ? n_cu : 256) * 4), dim3(256), 0, stream, a, 16);
     if ((err = hipGetLastError()) != hipSuccess) return err;
-    if (n_outcomes > 1) return launch_regress_multi(f, stream);
-    if (f.wave_regress && (err = launch_regress_wave(f, stream)) != hipSuccess) return err;
-    if (outcome_f64) {   // trk_assoc_scan_multi with one outcome
-        hipLaunchKernelGGL(k_assoc_outcome_copy, dim3((b.n_loci + 255) / 256), dim3(256), 0, stream, out.locus_f64, outcome_f64,
-                           b.n_loci);
-        return hipGetLastError();
-    }
-    return hipSuccess;
+    return launch_assoc_logit(b, prm, out, a.vect, stream);
 }
 
 // one pass of the dosage kernels over the batch for the design `prm` (at most AS_MAXV rows): records into `workspace`

@@ -93,6 +93,14 @@ hipError_t launch_assoc_scan(const trk_batch& b, const trk_assoc_params& prm, co
                              void* workspace, int n_cu, hipStream_t stream, int n_outcomes = 1);
 hipError_t launch_assoc_finalize(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
                                  void* workspace, hipStream_t stream, int n_outcomes = 1, double* outcome_f64 = nullptr);
+// trk_assoc_scan_logistic: after prepare -> scan, the finaliser's filters / mean / std, then the Newton kernel
+// (trk_assoc_logit.hip) in place of the Cholesky regression.  The workspace is assoc_logit_workspace_bytes long: the
+// scan's, then the sample-major vector block the Newton kernel reads.
+size_t assoc_logit_workspace_bytes(const trk_batch& b, int n_vec);
+hipError_t launch_assoc_finalize_logit(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out,
+                                       void* workspace, int n_cu, hipStream_t stream);
+hipError_t launch_assoc_logit(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_out& out, const double* vect,
+                              hipStream_t stream);
 hipError_t launch_assoc_dosage(const trk_batch& b, const trk_assoc_params& prm, const trk_assoc_dosage& dos,
                                const trk_assoc_out& out, double* class_sums, double* locus_sums, void* workspace,
                                hipStream_t stream);

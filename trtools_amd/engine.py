@@ -821,7 +821,7 @@ class Engine:
 
     # ---- scalar helpers ----
     # ---- associaTR scan ----
-    def assoc_scan(self, batch, vec, allele_len, rlen_class, sample_in=None, non_major_cutoff=20.0, out=None):
+    def assoc_scan(self, batch, vec, allele_len, rlen_class, sample_in=None, non_major_cutoff=20.0, out=None, entry=None):
         """trk_assoc_scan: vec [M, S] float64 (row 0 the standardised outcome, rows 1.. covariates),
         allele_len [sumA] float64, rlen_class [sumA] uint16, sample_in [S] uint8 or None.
         Returns AssocResult (device arrays locus_int [L, AI_COLS], locus_f64 [L, AF_COLS], allele_count [sumA])."""
@@ -842,8 +842,32 @@ class Engine:
         prm.sample_in = in_d.ptr if in_d is not None else None
         prm.non_major_cutoff = float(non_major_cutoff)
         out._keep = (vec_d, len_d, rc_d, in_d)
-        self._chk(self.lib.trk_assoc_scan(self.ctx, C.byref(batch.struct), C.byref(prm), C.byref(out.struct)))
+        entry = entry if entry is not None else self.lib.trk_assoc_scan   # (assoc_scan_logistic: the same structs)
+        self._chk(entry(self.ctx, C.byref(batch.struct), C.byref(prm), C.byref(out.struct)))
         return out
+
+    def assoc_scan_logistic(self, batch, vec, allele_len, rlen_class, sample_in=None, non_major_cutoff=20.0,
+                            outcome_checked=False):
+        """trk_assoc_scan_logistic: vec [1 + K, S] float64, row 0 the RAW 0/1 outcome, rows 1.. the standardised
+        covariates (K <= ASSOC_MAX_LOGIT_COVARS); the other arguments and the result as assoc_scan, with the Newton
+        fit's columns (AF_LOGLIK, AI_N_ITER; AS_CONSTANT_OUTCOME / AS_NOT_CONVERGED) in place of the OLS ones.
+        ValueError when the outcome holds anything but 0 or 1 on the regression set (``outcome_checked``: the caller
+        has looked already -- DeviceCompute does on its host copy, once per run)."""
+        if not outcome_checked:
+            self.check_binary_outcome(vec, sample_in)
+        return self.assoc_scan(batch, vec, allele_len, rlen_class, sample_in=sample_in, non_major_cutoff=non_major_cutoff,
+                               entry=self.lib.trk_assoc_scan_logistic)
+
+    @staticmethod
+    def check_binary_outcome(vec, sample_in=None):
+        """ValueError unless row 0 of ``vec`` is 0 or 1 wherever ``sample_in`` (None: everywhere) is set."""
+        vec_h = vec.get() if isinstance(vec, DeviceArray) else np.asarray(vec, dtype=np.float64)
+        y = vec_h[0] if vec_h.ndim == 2 and vec_h.shape[0] else vec_h.reshape(-1)[:0]
+        if sample_in is not None:
+            sin_h = sample_in.get() if isinstance(sample_in, DeviceArray) else np.asarray(sample_in)
+            y = y[sin_h.astype(bool)]
+        if not np.all((y == 0.0) | (y == 1.0)):
+            raise ValueError("assoc_scan_logistic: the outcome (vec[0]) must be 0 or 1 for every sample of the regression set")
 
     def assoc_scan_multi(self, batch, vec, n_outcomes, allele_len, rlen_class, sample_in=None, non_major_cutoff=20.0):
         """trk_assoc_scan_multi: vec [T + K, S] float64, rows 0..T-1 the standardised outcomes, rows T.. the covariates
